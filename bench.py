@@ -1,6 +1,15 @@
 """Benchmark: CTR training examples/sec of the fused HIP step (BASELINE.json metric).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--config c3|c2|c4|c5] [--no-cpu-baseline]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--config c3|c2|c4|c5]
+                    [--dump-outputs DIR] [--full [--no-cpu-baseline] [--no-driver-loop]]
+
+A plain run does only what the headline figure needs: set-up, W warm-up steps, the K timed
+steps (and the deferred flush), the JSON line with `value` and `ms_per_step`. --dump-outputs
+DIR then writes what the timed region's last step left a caller — the loss and the parameters
+(large tables as a fixed, seeded sample of rows) — as DIR/<name>.npy; the inputs are a pure
+function of the arguments, so two builds can be compared output for output. --full adds
+everything else described below: the un-timed breakdown and roofline passes, the driver-loop
+measurement, the sharding report and the CPU baseline.
 
 N>1 is launched by the driver as `python -m torch.distributed.run --nproc-per-node N ...`:
 one process per GPU, RCCL over xGMI, data parallel with row-sharded embedding tables
@@ -20,7 +29,7 @@ one episode over the ranks with the single-process result (pg_model.py).
 c5 = configs[4]: FM, Avazu-shape 22 fields, 40M vocab, dim 128, batch 8192 per GPU; N>1
 row-shards the table across the ranks (all-to-all), the configuration it is quoted on.
 
-The JSON line carries `roofline` for the dominant kernel group of the step — chosen by an
+With --full the JSON line carries `roofline` for the dominant kernel group of the step — chosen by an
 un-timed breakdown pass among the MLP GEMMs (C3/IPNN: gemm_planes_kernel, fp32-equivalent
 TFLOP/s against the fp32 MFMA peak), the deferred-Adam flush (C2/C5: deferred_flush_tile,
 HBM GB/s: 24 B per element + 8 B per row), the gather, the sparse plan, the scatter and the
@@ -155,6 +164,59 @@ def step_model(kind, B, F, K, U, H1=300, H2=200, flush_bytes_per_step=0.0, lin=T
     return parts, flops
 
 
+DUMP_LIMIT_BYTES = 64 << 20   # --dump-outputs: every file together
+DUMP_FULL_BYTES = 4 << 20     # a tensor up to this size is written whole, a larger one sampled
+DUMP_SAMPLE_ROWS = 32768
+
+
+def sample_rows(n_rows: int, ids=None) -> np.ndarray:
+    """The rows of a large table that --dump-outputs writes: DUMP_SAMPLE_ROWS drawn with a
+    fixed seed over the whole table and, with `ids` (the last timed batch's, the rows its
+    step updated), as many of those (a seeded choice when there are more); sorted, distinct."""
+    rng = np.random.default_rng(20240)
+    rows = rng.integers(0, n_rows, size=min(n_rows, DUMP_SAMPLE_ROWS))
+    if ids is not None:
+        u = np.unique(np.asarray(ids).reshape(-1))
+        u = u[(u >= 0) & (u < n_rows)]
+        if u.size > DUMP_SAMPLE_ROWS:
+            u = rng.choice(u, DUMP_SAMPLE_ROWS, replace=False)
+        rows = np.concatenate([rows, u])
+    return np.unique(rows).astype(np.int64)
+
+
+def collect_outputs(state: dict, scalars: dict, table_ids=None, table_rows=None) -> dict:
+    """{name: float32/float64 host array} of what the last timed step left a caller: the
+    scalars (losses) and every tensor of `state` (a state_dict), a tensor above
+    DUMP_FULL_BYTES as its sample_rows() rows with the row numbers beside it
+    (`<name>.rows`, float64: exact below 2^53). Copies now: later passes train on."""
+    out = {k: v.detach().to("cpu", torch.float64).numpy().copy() for k, v in scalars.items()}
+    for name, t in state.items():
+        t = t.detach()
+        if not t.is_floating_point():
+            continue
+        if t.numel() * t.element_size() > DUMP_FULL_BYTES and t.dim() >= 1:
+            # the tables indexed by the batch's ids (`table_rows` rows): those rows as well
+            ids = table_ids if t.shape[0] == table_rows else None
+            rows = sample_rows(t.shape[0], ids)
+            out[name + ".rows"] = rows.astype(np.float64)
+            t = t[torch.from_numpy(rows).to(t.device)]
+        dt = torch.float64 if t.dtype == torch.float64 else torch.float32
+        out[name] = t.to("cpu", dt).numpy().copy()
+    return out
+
+
+def dump_outputs(out_dir: str, arrays: dict) -> None:
+    total = sum(a.nbytes for a in arrays.values())
+    if total > DUMP_LIMIT_BYTES:
+        raise RuntimeError(f"--dump-outputs: {total} bytes exceed the {DUMP_LIMIT_BYTES} limit")
+    d = Path(out_dir)
+    d.mkdir(parents=True, exist_ok=True)
+    for name, a in arrays.items():
+        assert a.dtype in (np.float32, np.float64), (name, a.dtype)
+        np.save(d / f"{name}.npy", a)
+    log(f"wrote {len(arrays)} arrays ({total / 1e6:.1f} MB) to {d}")
+
+
 def cpu_model() -> str:
     try:
         for line in open("/proc/cpuinfo"):
@@ -279,7 +341,7 @@ def bench_pg(args, cfg, world, rank, dev):
 
     for i in range(args.warmup):
         step(i)
-    # roofline pass (not timed): HIP events around every policy GEMM launch
+    # --full: roofline pass (not timed), HIP events around every policy GEMM launch
     spans = []
     real_gemm = hip_ops.gemm
 
@@ -306,9 +368,6 @@ def bench_pg(args, cfg, world, rank, dev):
     # hip_ops.linear calls hip_ops.gemm through the module, so wrapping gemm sees every launch;
     # the breakdown runs eagerly (a graph replay cannot carry timing events)
     real_planes = hip_ops.gemm_planes
-    hip_ops.gemm = timed(real_gemm, gemm_flops)
-    hip_ops.gemm_planes = timed(real_planes, planes_flops)
-    pg.use_graphs = False
     fe_ev = []
     real_fe = hip_ops.feature_embedding
 
@@ -320,16 +379,20 @@ def bench_pg(args, cfg, world, rank, dev):
         fe_ev.append((e0, e1))
         return out
 
-    hip_ops.feature_embedding = fe_wrap
-    try:
-        n_bd = max(1, min(args.steps, args.breakdown_steps))
-        for i in range(n_bd):
-            step(i)
-        torch.cuda.synchronize()
-    finally:
-        hip_ops.gemm, hip_ops.feature_embedding = real_gemm, real_fe
-        hip_ops.gemm_planes = real_planes
-        pg.use_graphs = True
+    if args.full:
+        hip_ops.gemm = timed(real_gemm, gemm_flops)
+        hip_ops.gemm_planes = timed(real_planes, planes_flops)
+        pg.use_graphs = False
+        hip_ops.feature_embedding = fe_wrap
+        try:
+            n_bd = max(1, min(args.steps, args.breakdown_steps))
+            for i in range(n_bd):
+                step(i)
+            torch.cuda.synchronize()
+        finally:
+            hip_ops.gemm, hip_ops.feature_embedding = real_gemm, real_fe
+            hip_ops.gemm_planes = real_planes
+            pg.use_graphs = True
 
     if world > 1:
         dist.barrier()
@@ -346,13 +409,10 @@ def bench_pg(args, cfg, world, rank, dev):
         t = torch.tensor([elapsed], dtype=torch.float64, device=dev)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t.item())
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, collect_outputs(
+            pg.policy_net.state_dict(), {"loss_last_step": loss.reshape(1)}))
 
-    g_ms = [a.elapsed_time(b) for a, b, _ in spans]
-    flops = sum(w for _, _, w in spans) / len(spans)
-    launch_ms = sum(g_ms) / len(g_ms)
-    achieved = flops / (launch_ms * 1e-3) / 1e12
-    fe_ms = sum(a.elapsed_time(b) for a, b in fe_ev) / len(fe_ev)
-    fe_bytes = B * F * 8 + B * F * 4 * K + B * (F * (F - 1) // 2 + F * K) * 4
     result = {
         "metric": METRIC, "value": world * B * args.steps / elapsed, "unit": "transitions/s",
         "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
@@ -366,26 +426,36 @@ def bench_pg(args, cfg, world, rank, dev):
                        " (one episode split over the ranks: reward all-gather, gradient "
                        "all-reduce)" if world > 1 else ""),
                    "optimizer": "Adam lr=1e-4 wd=1e-5 (PG_model.py:87)"},
-        "roofline": {"kernel": "policy MLP GEMMs fwd + bwd, averaged per launch "
-                               "(gemm_planes_kernel on the 741-1024-512-256 layers, "
-                               "ctr_gemm_f32_ex on the 256-128-A tail)",
-                     "bound": "mfma", "achieved": achieved, "peak": MFMA_F32_PEAK_TFS,
-                     "unit": "TFLOP/s", "frac": achieved / MFMA_F32_PEAK_TFS,
-                     "algorithmic_flops_per_launch": flops,
-                     "traffic": load_traffic("c4", "gemm")[0],
-                     "traffic_source": load_traffic("c4", "gemm")[1],
-                     "avg_launch_ms": launch_ms, "launches_timed": len(spans),
-                     "timing": "HIP events on the launch stream around each GEMM launch over "
-                               "un-timed learn() calls before the timed region"},
-        "kernels": {"feature_embedding_kernel": {"ms_per_call": fe_ms,
-                                                 "GBps": fe_bytes / (fe_ms * 1e-3) / 1e9},
-                    "policy GEMMs": {"ms_per_step": sum(g_ms) / n_bd}},
         "_graphs": "timed region: every learn() replays one HIP graph after the zero-std "
                    "check of the returns (one host sync); breakdown: eager launches",
         "last_loss": float(loss.item()),
-        "cpu_baseline": None,
+        "full": bool(args.full),
     }
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.full:
+        g_ms = [a.elapsed_time(b) for a, b, _ in spans]
+        flops = sum(w for _, _, w in spans) / len(spans)
+        launch_ms = sum(g_ms) / len(g_ms)
+        achieved = flops / (launch_ms * 1e-3) / 1e12
+        fe_ms = sum(a.elapsed_time(b) for a, b in fe_ev) / len(fe_ev)
+        fe_bytes = B * F * 8 + B * F * 4 * K + B * (F * (F - 1) // 2 + F * K) * 4
+        result.update({
+            "roofline": {"kernel": "policy MLP GEMMs fwd + bwd, averaged per launch "
+                                   "(gemm_planes_kernel on the 741-1024-512-256 layers, "
+                                   "ctr_gemm_f32_ex on the 256-128-A tail)",
+                         "bound": "mfma", "achieved": achieved, "peak": MFMA_F32_PEAK_TFS,
+                         "unit": "TFLOP/s", "frac": achieved / MFMA_F32_PEAK_TFS,
+                         "algorithmic_flops_per_launch": flops,
+                         "traffic": load_traffic("c4", "gemm")[0],
+                         "traffic_source": load_traffic("c4", "gemm")[1],
+                         "avg_launch_ms": launch_ms, "launches_timed": len(spans),
+                         "timing": "HIP events on the launch stream around each GEMM launch "
+                                   "over un-timed learn() calls before the timed region"},
+            "kernels": {"feature_embedding_kernel": {"ms_per_call": fe_ms,
+                                                     "GBps": fe_bytes / (fe_ms * 1e-3) / 1e9},
+                        "policy GEMMs": {"ms_per_step": sum(g_ms) / n_bd}},
+            "cpu_baseline": None,
+        })
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         log("cpu baseline ...")
         result["cpu_baseline"] = cpu_baseline_pg(cfg, host)
     if rank == 0:
@@ -445,7 +515,15 @@ def main():
     ap.add_argument("--steps", type=int, default=30)
     ap.add_argument("--warmup", type=int, default=5)
     ap.add_argument("--config", default="c3", choices=sorted(CONFIGS))
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also run what the headline figure does not need: the un-timed kernel "
+                         "breakdown and roofline passes, the driver-loop measurement, the "
+                         "sharding report and the CPU baseline (more keys in the JSON line)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step left a caller (loss, parameters; large "
+                         "tables as a fixed seeded sample of rows) as DIR/<name>.npy")
+    ap.add_argument("--no-cpu-baseline", action="store_true",
+                    help="--full without the CPU baseline")
     ap.add_argument("--batches", type=int, default=0,
                     help="0 (default): a fresh synthetic batch for every step (streaming, as the "
                          "reference trains: all_main/pretrain_main.py:71-78); N > 0: N distinct "
@@ -454,7 +532,8 @@ def main():
                     help="deferred Adam: flush every N steps (bounded staleness; default: the "
                          "trainer's, CTR_FLUSH_EVERY or 32; 0 = only at the region end)")
     ap.add_argument("--breakdown-steps", type=int, default=10,
-                    help="un-timed steps with every kernel group instrumented (kernel table)")
+                    help="--full: un-timed steps with every kernel group instrumented (kernel "
+                         "table)")
     ap.add_argument("--sharding", default="auto", choices=["auto", "rows", "replicated"],
                     help="N>1: row-sharded tables with all-to-all (auto) or, for comparison only "
                          "(eager, a host read per step), replicated tables "
@@ -469,8 +548,8 @@ def main():
                     help="deferred-exact dense Adam (default) or the dense streaming pass; "
                          "bitwise-identical results (tests/test_gpu_deferred.py)")
     ap.add_argument("--no-driver-loop", action="store_true",
-                    help="skip the driver-loop measurement (pretrain_main.run_epoch over K "
-                         "batches after the timed region)")
+                    help="--full without the driver-loop measurement (pretrain_main.run_epoch "
+                         "over K batches after the timed region)")
     ap.add_argument("--no-graphs", action="store_true",
                     help="launch every step eagerly (no HIP-graph replay): the host-paced "
                          "launch path (N > 1 row sharding over gloo, or CTR_SHARDED_GRAPHS=0)")
@@ -507,10 +586,10 @@ def main():
                  "IPNN": lambda: InnerPNN(V, F, K)}[cfg["kind"]]()
     model.train()
     synth = CriteoSynth(V, F, seed=1)
-    n_bd = max(1, min(args.steps, args.breakdown_steps))
-    # streaming (default): every step of the warm-up, the breakdown pass and the timed region
-    # trains on a batch of its own (the roofline pass after the region revisits the timed
-    # region's batches); the HIP graphs are keyed by input slot, not by batch
+    n_bd = max(1, min(args.steps, args.breakdown_steps)) if args.full else 0
+    # streaming (default): every step of the warm-up, the breakdown pass (--full) and the timed
+    # region trains on a batch of its own (the roofline pass after the region revisits the
+    # timed region's batches); the HIP graphs are keyed by input slot, not by batch
     n_batches = args.batches if args.batches > 0 else args.warmup + n_bd + 3 + args.steps
     t_gen = time.perf_counter()
     host_batches = synth.stream(n_batches, B, rank=rank, threads=min(16, os.cpu_count() or 1))
@@ -547,32 +626,22 @@ def main():
     for i in range(args.warmup):
         step(i)
 
-    def total_ms(spans):
-        return float(sum(a.elapsed_time(b) for a, b, _ in spans))
-
-    def avg_ms(spans):
-        return total_ms(spans) / len(spans) if spans else float("nan")
-
-    # breakdown pass (NOT timed): every kernel group bracketed by HIP events, to find the
-    # dominant kernel and report the per-kernel table
-    keys = ("adam", "catchup", "gather", "plan", "scatter", "flush", "gemm", "exchange")
+    # the timed region starts, with and without --full, from tables with no step owed
     trainer.flush()
-    trainer.timing = {k: [] for k in keys}
-    for i in range(n_bd):
-        step(i)
-    trainer.flush()
-    torch.cuda.synchronize()
-    bd, trainer.timing = trainer.timing, None
-    per_step = {k: total_ms(v) / n_bd for k, v in bd.items()}
-    # N = 1 deferred: the embedding Adam apply runs inside the scatter's combine pass
-    fused_apply = (world == 1 and args.optimizer == "deferred" and isinstance(
-        trainer, FusedCTRTrainer) and not isinstance(trainer, ShardedCTRTrainer)
-        and trainer.fuse_apply and trainer._vec_ok and trainer.K >= 32)
-    dominant = max(("adam", "catchup", "gather", "plan", "scatter", "gemm", "flush"),
-                   key=lambda k: per_step[k])
+    bd = None
+    if args.full:
+        # breakdown pass (NOT timed): every kernel group bracketed by HIP events, to find the
+        # dominant kernel and report the per-kernel table
+        keys = ("adam", "catchup", "gather", "plan", "scatter", "flush", "gemm", "exchange")
+        trainer.timing = {k: [] for k in keys}
+        for i in range(n_bd):
+            step(i)
+        trainer.flush()
+        torch.cuda.synchronize()
+        bd, trainer.timing = trainer.timing, None
 
     # re-warm (untimed), only with the pipelined weight-gradient tail (CTR_PIPELINE_WGRAD=1):
-    # the breakdown's flush left no tail pending; a few graph-replayed steps restore the
+    # the flush above left no tail pending; a few graph-replayed steps restore the
     # steady state the timed region runs in (every graph it replays captured before it
     # starts), and a flush after them keeps the region's own flush at K replayed steps
     trainer.timing = None
@@ -605,6 +674,73 @@ def main():
         t = torch.tensor([elapsed], dtype=torch.float64, device=dev)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t.item())
+    if args.dump_outputs and rank == 0:
+        # after the region's flush every parameter is the reference's after the last step;
+        # N > 1: rank 0's shard of the tables
+        last_ids = host_batches[(seq[0] - 1) % len(host_batches)][0] if world == 1 else None
+        dump_outputs(args.dump_outputs, collect_outputs(
+            model.state_dict(),
+            {"loss_last_step": trainer._bufs.loss, "loss_sum": trainer.loss_sum},
+            table_ids=last_ids, table_rows=model.feature_embedding.weight.shape[0]))
+
+    result = {
+        "metric": METRIC, "value": world * B * args.steps / elapsed, "unit": "examples/s",
+        "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
+        "ms_per_step": elapsed / args.steps * 1e3,
+        "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": "f32",
+        "data": "synthetic (Criteo-shape ids: skewed field cardinalities, Zipf(1.1); "
+                "planted-FM labels, CTR~0.25); random-init weights",
+        "config": {"workload": cfg["workload"], "model": cfg["kind"], "global_batch": B * world,
+                   "fields": F, "vocab": V, "embed_dim": K,
+                   "parallelism": f"dp{world}" + (
+                       " (row-sharded tables: ids/rows/row-grads by all-to-all, dense grads "
+                       "all-reduce)" if sharding == "rows" else
+                       " (replicated tables, sparse row-grad all-gather)" if world > 1 else ""),
+                   "optimizer": f"dense Adam lr=1e-3 wd=1e-5 (reference semantics), "
+                                f"{args.optimizer} mode",
+                   "batches": ("fresh: one synthetic batch per step" if args.batches <= 0
+                               else f"{args.batches} distinct, cycled"),
+                   "flush_every": getattr(trainer, "flush_every", None),
+                   "plan_lookahead": (args.lookahead if isinstance(trainer, ShardedCTRTrainer)
+                                      or (getattr(trainer, "plan_lookahead", False)
+                                          and args.optimizer == "deferred") else 0)},
+        "host_ms_per_step": host_s / args.steps * 1e3,  # inside step(): the enqueue cost
+        "graph_captures": {"total": getattr(trainer, "captures", None),
+                           "in_timed_region": captures_region,
+                           "graphs_held": len(getattr(trainer, "_graphs", {}))},
+        "full": bool(args.full),
+    }
+    if args.full:
+        result.update(full_report(args, cfg, world, rank, trainer, step, seq, xs, ys, bd, n_bd,
+                                  elapsed, host_batches))
+    if rank == 0:
+        print(json.dumps(result), flush=True)
+    if world > 1:
+        dist.barrier()
+        dist.destroy_process_group()
+
+
+def full_report(args, cfg, world, rank, trainer, step, seq, xs, ys, bd, n_bd, elapsed,
+                host_batches) -> dict:
+    """--full, after the timed region: the roofline pass, the driver-loop measurement, the
+    kernel table of the breakdown pass `bd`, the step roofline, the sharding report and the
+    CPU baseline; returns the keys they add to the JSON line."""
+    from rl_ctr_prediction_amd import FusedCTRTrainer, ShardedCTRTrainer
+    V, F, K, B = cfg["V"], cfg["F"], cfg["K"], cfg["B"]
+
+    def total_ms(spans):
+        return float(sum(a.elapsed_time(b) for a, b, _ in spans))
+
+    def avg_ms(spans):
+        return total_ms(spans) / len(spans) if spans else float("nan")
+
+    per_step = {k: total_ms(v) / n_bd for k, v in bd.items()}
+    # N = 1 deferred: the embedding Adam apply runs inside the scatter's combine pass
+    fused_apply = (world == 1 and args.optimizer == "deferred" and isinstance(
+        trainer, FusedCTRTrainer) and not isinstance(trainer, ShardedCTRTrainer)
+        and trainer.fuse_apply and trainer._vec_ok and trainer.K >= 32)
+    dominant = max(("adam", "catchup", "gather", "plan", "scatter", "gemm", "flush"),
+                   key=lambda k: per_step[k])
     # roofline pass: the same K steps again, launched eagerly with HIP events recorded on
     # the launch stream around every launch of the dominant kernel group (a HIP graph
     # cannot carry timing events: hipErrorInvalidHandle); kernel durations do not depend
@@ -753,7 +889,6 @@ def main():
     else:
         g_kernel, g_bytes = "fm_forward_vec (gather + FM" + (
             ", MLP input as bf16 planes)" if deep else ")"), gather_bytes(S, K, B, deep)
-    value = world * B * args.steps / elapsed
     # the step against the machine: every byte and flop of the algorithm the region times
     # (deferred-exact dense Adam; the flushes inside the region amortised over its steps)
     n_flush = len(timing["flush"])
@@ -779,32 +914,9 @@ def main():
     if world > 1:
         step_roofline["_note"] = "N > 1: per rank; the exchange's bytes are not in the model"
     result = {
-        "metric": METRIC, "value": value, "unit": "examples/s", "n_gpus": world,
-        "steps": args.steps, "warmup": args.warmup, "ms_per_step": elapsed / args.steps * 1e3,
-        "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": "f32",
-        "data": "synthetic (Criteo-shape ids: skewed field cardinalities, Zipf(1.1); "
-                "planted-FM labels, CTR~0.25); random-init weights",
-        "config": {"workload": cfg["workload"], "model": cfg["kind"], "global_batch": B * world,
-                   "fields": F, "vocab": V, "embed_dim": K,
-                   "parallelism": f"dp{world}" + (
-                       " (row-sharded tables: ids/rows/row-grads by all-to-all, dense grads "
-                       "all-reduce)" if sharding == "rows" else
-                       " (replicated tables, sparse row-grad all-gather)" if world > 1 else ""),
-                   "optimizer": f"dense Adam lr=1e-3 wd=1e-5 (reference semantics), "
-                                f"{args.optimizer} mode",
-                   "batches": ("fresh: one synthetic batch per step" if args.batches <= 0
-                               else f"{args.batches} distinct, cycled"),
-                   "flush_every": getattr(trainer, "flush_every", None),
-                   "plan_lookahead": (args.lookahead if isinstance(trainer, ShardedCTRTrainer)
-                                      or (getattr(trainer, "plan_lookahead", False)
-                                          and args.optimizer == "deferred") else 0)},
         "roofline": roofline,
         "step_roofline": step_roofline,
         "kernels": kernels,
-        "host_ms_per_step": host_s / args.steps * 1e3,  # inside step(): the enqueue cost
-        "graph_captures": {"total": getattr(trainer, "captures", None),
-                           "in_timed_region": captures_region,
-                           "graphs_held": len(getattr(trainer, "_graphs", {}))},
         "driver_loop": driver,
         "gather_scatter": {
             "gather_kernel": g_kernel, "gather_ms": gather_ms,
@@ -857,11 +969,7 @@ def main():
         cc = load_crosscal(args.config)
         if cc is not None:  # how the port's CPU time compares with the reference's own
             result["cpu_baseline"]["cross_calibration"] = cc
-    if rank == 0:
-        print(json.dumps(result), flush=True)
-    if world > 1:
-        dist.barrier()
-        dist.destroy_process_group()
+    return result
 
 
 if __name__ == "__main__":

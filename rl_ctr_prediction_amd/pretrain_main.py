@@ -137,7 +137,7 @@ def train(model, optimizer, data_loader, loss, device):
 
 def run_epoch(optimizer, batches) -> float:
     """Mean train loss of one pass of `optimizer` over `batches` [(features, labels)] in
-    order (the body of train(); bench.py --driver-loop times it)."""
+    order (the body of train(); bench.py --full times it)."""
     if not batches:
         raise ZeroDivisionError("float division by zero")  # the reference's empty epoch
     lookahead = isinstance(optimizer, FusedCTRTrainer)
