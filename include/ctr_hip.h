@@ -630,6 +630,34 @@ int ctr_ipnn_backward(const void* idx, int idx_type, int64_t B, int F, int K, in
                       const float* emb, const float* dcat, int64_t ldd, float* dslot,
                       ctr_stream_t stream);
 
+/* ------------------------------------------------ DCN: the cross network --------------
+ * For B examples with x0 = flat(E[x_b]) [D] (row stride ldx), W and bias [L, D] contiguous
+ * (the stacked cross_net_w[i].weight and cross_net_b[i]), 1 <= L <= 8:
+ *   x_0 = x0;  s_i = <x_i, W_i>;  x_{i+1} = (x0 * s_i + bias_i) + x_i   (that association,
+ *   no fma contraction: p_model.py:427-429).
+ * ctr_dcn_cross_forward: s [B, L] (all the backward keeps besides x0), and at least one of
+ *   xL [B, D] (row stride ldo) = x_L and z [B] = <x_L, w_tail> (needs w_tail [D], the first D
+ *   columns of DCN.linear.weight: the cross half of p_model.py:431-433, so that neither x_L
+ *   nor cat[x_L, dn] is materialised). x0 is read once; no x_i reaches memory.
+ * ctr_dcn_cross_backward: dL/dx_L = gL [B, D] (row stride ldg, optional) + gz[b] * w_tail
+ *   (the rank-1 form: gz and w_tail both or neither; at least one form). Outputs dx0 [B, D]
+ *   (row stride ldd), dW and dbias [L, D], and dw_tail [D] = sum_b gz[b] * x_L[b] (optional,
+ *   rank-1 form only). x0 (and gL) are read once. The batch sums are deterministic: per-block
+ *   partials in row order in ws (ctr_dcn_cross_workspace_bytes, independent of B, 16-byte
+ *   aligned), added in block order by a second launch; no float atomics. B == 0 zero-fills
+ *   dW, dbias and dw_tail.
+ * A row's s, x_L, z and dx0 do not depend on B or on the row's position. Vector (16-byte)
+ * accesses are used when D, the strides and the pointers allow, scalar ones otherwise. */
+int64_t ctr_dcn_cross_workspace_bytes(int64_t B, int D, int L);
+int ctr_dcn_cross_forward(int64_t B, int D, int L, const float* x0, int64_t ldx,
+                          const float* W, const float* bias, const float* w_tail, float* s,
+                          float* xL, int64_t ldo, float* z, ctr_stream_t stream);
+int ctr_dcn_cross_backward(int64_t B, int D, int L, const float* x0, int64_t ldx,
+                           const float* W, const float* bias, const float* s,
+                           const float* gL, int64_t ldg, const float* gz, const float* w_tail,
+                           float* dx0, int64_t ldd, float* dW, float* dbias, float* dw_tail,
+                           void* ws, int64_t ws_bytes, ctr_stream_t stream);
+
 /* ------------------------------------------------------ A8: REINFORCE (PG) -----------
  * ctr_softmax_rows: out[b,:] = softmax(x[b,:]) (PG_model.py:56).
  * ctr_pg_discount_norm: discounted return of an episode, reverse recurrence

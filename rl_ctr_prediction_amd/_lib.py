@@ -226,6 +226,11 @@ SIGNATURES = {
     "ctr_ipnn_forward_planes": (_i32, [_vp, _i32, _i64, _i32, _i32, _i64, _vp, _vp, _i64,
                                        _planes_p, _vp, _vp]),
     "ctr_ipnn_backward": (_i32, [_vp, _i32, _i64, _i32, _i32, _i64, _vp, _vp, _i64, _vp, _vp]),
+    "ctr_dcn_cross_workspace_bytes": (_i64, [_i64, _i32, _i32]),
+    "ctr_dcn_cross_forward": (_i32, [_i64, _i32, _i32, _vp, _i64, _vp, _vp, _vp, _vp, _vp, _i64,
+                                     _vp, _vp]),
+    "ctr_dcn_cross_backward": (_i32, [_i64, _i32, _i32, _vp, _i64, _vp, _vp, _vp, _vp, _i64, _vp,
+                                      _vp, _vp, _i64, _vp, _vp, _vp, _vp, _i64, _vp]),
     "ctr_softmax_rows": (_i32, [_vp, _i64, _i32, _vp, _vp]),
     "ctr_pg_workspace_bytes": (_i64, [_i64]),
     "ctr_pg_discount_norm": (_i32, [_vp, _i64, _f64, _vp, _vp, _vp, _vp, _i64, _vp]),

@@ -23,6 +23,7 @@ __all__ = [
     "tensor_sum", "colsum", "transpose", "Planes", "split_planes", "gemm_planes", "SparsePlanBuffers", "fm_embedding_grad", "segment_sum_rows",
     "fm_embedding_grad_adam", "segment_sum_rows_adam",
     "rows_to_dense", "adam_dense", "fm_step_tail", "adam_embedding", "adam_scalars", "feature_embedding",
+    "dcn_cross_forward", "dcn_cross_backward",
     "AdamStepTable", "adam_deferred_rows", "adam_deferred_flush", "adam_deferred_catchup_ids",
     "step_begin", "step_end", "ids_add_", "shard_pack_ids", "shard_runs_copy",
     "softmax_rows", "pg_discount_norm", "pg_loss_grad", "pg_vt_mean", "pg_loss_grad_global", "check_index_error", "Workspace",
@@ -1096,6 +1097,96 @@ def ipnn_backward(idx: torch.Tensor, emb: torch.Tensor, dcat: torch.Tensor,
         out = torch.empty(B * F, K, dtype=torch.float32, device=emb.device)
     lib.ctr_ipnn_backward(_p(idx), it, B, F, K, V, _p(emb), _p(dcat), dcat.stride(0), _p(out),
                           _stream())
+    return out
+
+
+def _rows2d(t: torch.Tensor, name: str, B: int, D: int) -> torch.Tensor:
+    """A float32 device matrix with >= B rows of >= D unit-stride columns (rows may be
+    strided: a view into a wider buffer)."""
+    _dev(t, name)
+    if (t.dtype != torch.float32 or t.dim() != 2 or t.shape[0] < B or t.shape[1] < D
+            or (t.numel() and t.stride(1) != 1) or (B > 1 and t.stride(0) < D)):
+        raise ValueError(f"{name}: must be float32 [>= {B}, >= {D}] with unit column stride")
+    return t
+
+
+def _dcn_params(W, bias, w_tail):
+    _f32(W, "W")
+    _f32(bias, "bias")
+    if W.dim() != 2 or bias.shape != W.shape:
+        raise ValueError("dcn_cross: W and bias must both be [L, D]")
+    L, D = W.shape
+    if w_tail is not None:
+        _f32(w_tail, "w_tail")
+        if w_tail.numel() != D:
+            raise ValueError(f"dcn_cross: w_tail must have {D} elements")
+    return L, D
+
+
+def dcn_cross_forward(x0: torch.Tensor, W: torch.Tensor, bias: torch.Tensor,
+                      w_tail: torch.Tensor | None = None, *, want_xl: bool | None = None,
+                      out: dict | None = None) -> dict:
+    """DCN's cross network (p_model.py:426-429) over x0 [B, D] with the stacked W, bias [L, D]:
+    dict(s [B, L], xL [B, D] or None, z [B] = <x_L, w_tail> or None). want_xl defaults to
+    "no w_tail given"; with w_tail and want_xl=False x_L is never written."""
+    L, D = _dcn_params(W, bias, w_tail)
+    if x0.dim() != 2 or x0.shape[1] != D:
+        raise ValueError(f"dcn_cross_forward: x0 must be [B, {D}]")
+    B = x0.shape[0]
+    _rows2d(x0, "x0", B, D)
+    if want_xl is None:
+        want_xl = w_tail is None
+    if out is None:
+        e = lambda *s: torch.empty(*s, dtype=torch.float32, device=x0.device)  # noqa: E731
+        out = dict(s=e(B, L), xL=e(B, D) if want_xl else None,
+                   z=e(B) if w_tail is not None else None)
+    xL, z = out.get("xL"), out.get("z")
+    _f32(out["s"], "s")
+    if xL is not None:
+        _rows2d(xL, "xL", B, D)
+    if z is not None:
+        _f32(z, "z")
+    lib.ctr_dcn_cross_forward(B, D, L, _p(x0), x0.stride(0) if B else D, _p(W), _p(bias),
+                              _p(w_tail), _p(out["s"]), _p(xL),
+                              xL.stride(0) if xL is not None and B else D, _p(z), _stream())
+    return out
+
+
+def dcn_cross_backward(x0: torch.Tensor, W: torch.Tensor, bias: torch.Tensor, s: torch.Tensor,
+                       gL: torch.Tensor | None = None, gz: torch.Tensor | None = None,
+                       w_tail: torch.Tensor | None = None, out: dict | None = None) -> dict:
+    """Backward of dcn_cross_forward for dL/dx_L = gL [B, D] (optional) + gz[b] * w_tail (the
+    rank-1 form of DCN's final Linear; gz and w_tail together): dict(dx0 [B, D], dW [L, D],
+    dbias [L, D], dw_tail [D] or None). One kernel over the batch plus the deterministic
+    reduction of its per-block partials."""
+    L, D = _dcn_params(W, bias, w_tail)
+    if x0.dim() != 2 or x0.shape[1] != D:
+        raise ValueError(f"dcn_cross_backward: x0 must be [B, {D}]")
+    B = x0.shape[0]
+    _rows2d(x0, "x0", B, D)
+    _f32(s, "s")
+    if s.numel() != B * L:
+        raise ValueError(f"dcn_cross_backward: s must be [{B}, {L}]")
+    if gL is not None:
+        _rows2d(gL, "gL", B, D)
+    if gz is not None:
+        _f32(gz, "gz")
+        if gz.numel() != B:
+            raise ValueError(f"dcn_cross_backward: gz must have {B} elements")
+    if out is None:
+        e = lambda *sh: torch.empty(*sh, dtype=torch.float32, device=x0.device)  # noqa: E731
+        out = dict(dx0=e(B, D), dW=e(L, D), dbias=e(L, D), dw_tail=e(D) if gz is not None else None)
+    dx0 = _rows2d(out["dx0"], "dx0", B, D)
+    _f32(out["dW"], "dW")
+    _f32(out["dbias"], "dbias")
+    if out.get("dw_tail") is not None:
+        _f32(out["dw_tail"], "dw_tail")
+    ws = Workspace.get(lib.ctr_dcn_cross_workspace_bytes(B, D, L), x0.device)
+    lib.ctr_dcn_cross_backward(B, D, L, _p(x0), x0.stride(0) if B else D, _p(W), _p(bias), _p(s),
+                               _p(gL), gL.stride(0) if gL is not None and B else D, _p(gz),
+                               _p(w_tail), _p(dx0), dx0.stride(0) if B else D, _p(out["dW"]),
+                               _p(out["dbias"]), _p(out.get("dw_tail")), _p(ws), ws.numel(),
+                               _stream())
     return out
 
 

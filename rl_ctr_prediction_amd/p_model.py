@@ -1,6 +1,8 @@
-"""FM, FFM, DeepFM and InnerPNN with the reference's construction API, on the HIP kernels.
+"""FM, FFM, DeepFM, InnerPNN, FNN and DCN with the reference's construction API, on the HIP
+kernels.
 
-Drop-in for ``src/models/p_model.py`` (FM 28-57, FFM 59-100, InnerPNN 146-200, DeepFM 256-324): identical constructor
+Drop-in for ``src/models/p_model.py`` (FM 28-57, FFM 59-100, InnerPNN 146-200, DeepFM 256-324,
+FNN 326-373, DCN 376-435): identical constructor
 signatures, submodules created in the same order (so ``torch.manual_seed(s)`` gives the
 same initial weights as the reference) and identical state_dict keys, so the RL drivers'
 ``torch.load('...FMbest.pth')`` / ``load_state_dict`` and ``Feature_Embedding.load_embedding``
@@ -17,6 +19,7 @@ from __future__ import annotations
 
 import itertools
 
+import numpy as np
 import torch
 import torch.nn as nn
 
@@ -28,6 +31,12 @@ _seed_counter = itertools.count()
 def _dropout_seed() -> int:
     # deterministic under torch.manual_seed, distinct per call site
     return (torch.initial_seed() * 1000003 + next(_seed_counter) * 7919) & (2**63 - 1)
+
+
+def _rng_dropout_seed() -> int:
+    # drawn from torch's generator, like the reference's dropout masks: two forwards after
+    # the same torch.manual_seed drop the same elements (FNN, DCN)
+    return int(torch.randint(0, 2**62, (1,)).item())
 
 
 class _FMPart(torch.autograd.Function):
@@ -137,12 +146,56 @@ class _FFMPart(torch.autograd.Function):
         return (None, g_lin, hip_ops.tensor_sum(gz).view(1), None, *g_tables)
 
 
+class _GatherFlat(torch.autograd.Function):
+    """flat(E[x]) [B, F*K] (p_model.py:370, 424: the gather + view of FNN and DCN). Backward:
+    the slot gradients summed per row in slot order (deterministic), returned dense like
+    embedding_dense_backward."""
+
+    @staticmethod
+    def forward(ctx, x, emb):
+        ctx.save_for_backward(x, emb)
+        B, F = x.shape
+        return hip_ops.embedding_gather(emb, x).view(B, F * emb.shape[1])
+
+    @staticmethod
+    def backward(ctx, gflat):
+        x, emb = ctx.saved_tensors
+        B, F = x.shape
+        V, K = emb.shape
+        plan = hip_ops.SparsePlanBuffers(B * F, emb.device).build(x, V)
+        grad_rows, _ = hip_ops.segment_sum_rows(plan, gflat.contiguous().view(B * F, K))
+        g_emb, _ = hip_ops.rows_to_dense(plan, V, grad_rows)
+        return None, g_emb
+
+
+class _CrossPart(torch.autograd.Function):
+    """z_cross [B,1] = <x_L, w_tail> of DCN's cross network (p_model.py:426-429 and the cross
+    columns of the final Linear, 431-433) on ctr_dcn_cross_forward; x_L is never written.
+    Saves x0 and the per-layer dots s; backward = one ctr_dcn_cross_backward in the rank-1
+    form (dL/dx_L = gz * w_tail)."""
+
+    @staticmethod
+    def forward(ctx, x0, W, b, w_tail):
+        x0 = x0.contiguous()
+        r = hip_ops.dcn_cross_forward(x0, W, b, w_tail, want_xl=False)
+        ctx.save_for_backward(x0, W, b, w_tail, r["s"])
+        return r["z"].view(-1, 1)
+
+    @staticmethod
+    def backward(ctx, gz):
+        x0, W, b, w_tail, s = ctx.saved_tensors
+        r = hip_ops.dcn_cross_backward(x0, W, b, s, gz=gz.reshape(-1).contiguous(), w_tail=w_tail)
+        return r["dx0"], r["dW"], r["dbias"], r["dw_tail"]
+
+
 def _fm_part(x, emb, lin, bias, want_emb):
     return _FMPart.apply(x, emb, lin, bias, want_emb)
 
 
-def mlp_forward(mlp: nn.Sequential, h: torch.Tensor, training: bool) -> torch.Tensor:
-    """Run an nn.Sequential of [Linear, ReLU, Dropout]* + Linear on fused HIP GEMMs."""
+def mlp_forward(mlp: nn.Sequential, h: torch.Tensor, training: bool,
+                seed_fn=_dropout_seed) -> torch.Tensor:
+    """Run an nn.Sequential of [Linear, ReLU, Dropout]* + Linear on fused HIP GEMMs; seed_fn
+    gives each dropout layer's seed."""
     mods = list(mlp)
     i = 0
     while i < len(mods):
@@ -156,7 +209,7 @@ def mlp_forward(mlp: nn.Sequential, h: torch.Tensor, training: bool) -> torch.Te
         if relu and j < len(mods) and isinstance(mods[j], nn.Dropout):
             drop = float(mods[j].p) if training else 0.0
             j += 1
-        h = _LinearAct.apply(h, lin.weight, lin.bias, relu, drop, _dropout_seed())
+        h = _LinearAct.apply(h, lin.weight, lin.bias, relu, drop, seed_fn())
         i = j
     return h
 
@@ -295,3 +348,119 @@ class FFM(nn.Module):
             z = hip_ops.ffm_forward(x, [t.detach() for t in tabs], ptrs,
                                     self.linear.weight.detach(), self.bias.detach())["z"]
             return torch.sigmoid(z).view(-1, 1)
+
+
+class FNN(nn.Module):
+    """p_model.py:326-373: MLP [F*K -> 300 -> 200 -> 1] (ReLU, Dropout 0.2) over the flat
+    embeddings (DeepFM's deep half alone); load_embedding takes the FM-pretrained table."""
+
+    def __init__(self, feature_nums, field_nums, latent_dims):
+        super().__init__()
+        latent_dims = int(latent_dims)
+        self.feature_nums = feature_nums
+        self.field_nums = field_nums
+        self.latent_dims = latent_dims
+        self.feature_embedding = nn.Embedding(self.feature_nums, self.latent_dims)
+        deep_input_dims = self.field_nums * self.latent_dims
+        layers = []
+        for neuron_num in (300, 200):
+            layers.append(nn.Linear(deep_input_dims, neuron_num))
+            layers.append(nn.ReLU())
+            layers.append(nn.Dropout(p=0.2))
+            deep_input_dims = neuron_num
+        layers.append(nn.Linear(deep_input_dims, 1))
+        self.mlp = nn.Sequential(*layers)
+
+    def load_embedding(self, pretrain_params):
+        self.feature_embedding.weight.data.copy_(
+            torch.from_numpy(np.array(pretrain_params["feature_embedding.weight"].cpu())))
+
+    def forward(self, x):
+        E = self.feature_embedding.weight
+        if torch.is_grad_enabled() and any(p.requires_grad for p in self.parameters()):
+            flat = _GatherFlat.apply(x, E)
+            seed_fn = _rng_dropout_seed if self.training else _dropout_seed
+            return torch.sigmoid(mlp_forward(self.mlp, flat, self.training, seed_fn))
+        with torch.no_grad():
+            B, F = x.shape
+            h = hip_ops.embedding_gather(E.detach(), x).view(B, F * E.shape[1])
+            m = self.mlp
+            p0 = m[2].p if self.training else 0.0
+            p1 = m[5].p if self.training else 0.0
+            seed_fn = _rng_dropout_seed if self.training else _dropout_seed
+            h = hip_ops.linear(h, m[0].weight, m[0].bias, relu=True, drop_p=p0,
+                               seed=seed_fn())
+            h = hip_ops.linear(h, m[3].weight, m[3].bias, relu=True, drop_p=p1,
+                               seed=seed_fn())
+            zero = torch.zeros(h.shape[0], dtype=torch.float32, device=h.device)
+            head = hip_ops.deepfm_head(h, m[6].weight, m[6].bias, zero)
+            return head["p"].view(-1, 1)
+
+
+class DCN(nn.Module):
+    """p_model.py:376-435: a 5-layer cross network x_{i+1} = x0 * <x_i, w_i> + b_i + x_i beside
+    the deep network DN [F*K -> 300 -> 200] (ReLU, Dropout 0.2), both over the flat embeddings;
+    p = sigmoid(linear(cat[x_5, dn])). The final Linear is split at column F*K: the cross
+    kernel emits <x_5, w[:F*K]> itself, so neither x_5 nor the concatenation is materialised."""
+
+    def __init__(self, feature_nums, field_nums, latent_dims, output_dim=1):
+        super().__init__()
+        latent_dims = int(latent_dims)
+        if output_dim != 1:
+            raise NotImplementedError("DCN: output_dim must be 1 (the reference's only use)")
+        self.feature_nums = feature_nums
+        self.field_nums = field_nums
+        self.latent_dims = latent_dims
+        self.feature_embedding = nn.Embedding(self.feature_nums, self.latent_dims)
+        deep_input_dims = self.field_nums * self.latent_dims
+        deep_net_layers = []
+        neural_nums = [300, 200]
+        self.num_neural_layers = 5
+        for neural_num in neural_nums:
+            deep_net_layers.append(nn.Linear(deep_input_dims, neural_num))
+            deep_net_layers.append(nn.ReLU())
+            deep_net_layers.append(nn.Dropout(p=0.2))
+            deep_input_dims = neural_num
+        self.DN = nn.Sequential(*deep_net_layers)
+        cross_input_dims = self.field_nums * self.latent_dims
+        self.cross_net_w = nn.ModuleList([
+            nn.Linear(cross_input_dims, output_dim, bias=False)
+            for _ in range(self.num_neural_layers)])
+        self.cross_net_b = nn.ParameterList([
+            nn.Parameter(torch.zeros((cross_input_dims,)))
+            for _ in range(self.num_neural_layers)])
+        self.linear = nn.Linear(neural_nums[-1] + cross_input_dims, output_dim)
+
+    def _cross_params(self):
+        W = torch.cat([lin.weight for lin in self.cross_net_w], dim=0)  # [L, D]
+        b = torch.stack(list(self.cross_net_b), dim=0)
+        return W, b
+
+    def forward(self, x):
+        E = self.feature_embedding.weight
+        D = self.field_nums * self.latent_dims
+        lw = self.linear.weight  # [1, D + 200]: cross columns, then deep columns
+        if torch.is_grad_enabled() and any(p.requires_grad for p in self.parameters()):
+            flat = _GatherFlat.apply(x, E)
+            W, b = self._cross_params()
+            z_cross = _CrossPart.apply(flat, W, b, lw[0, :D].contiguous())
+            seed_fn = _rng_dropout_seed if self.training else _dropout_seed
+            dn = mlp_forward(self.DN, flat, self.training, seed_fn)
+            z_deep = _LinearAct.apply(dn, lw[:, D:].clone(), self.linear.bias, False, 0.0, 0)
+            return torch.sigmoid(z_cross + z_deep)
+        with torch.no_grad():
+            B, F = x.shape
+            flat = hip_ops.embedding_gather(E.detach(), x).view(B, D)
+            W, b = self._cross_params()
+            z_cross = hip_ops.dcn_cross_forward(flat, W, b, lw[0, :D].contiguous(),
+                                                want_xl=False)["z"]
+            m = self.DN
+            p0 = m[2].p if self.training else 0.0
+            p1 = m[5].p if self.training else 0.0
+            seed_fn = _rng_dropout_seed if self.training else _dropout_seed
+            h = hip_ops.linear(flat, m[0].weight, m[0].bias, relu=True, drop_p=p0,
+                               seed=seed_fn())
+            h = hip_ops.linear(h, m[3].weight, m[3].bias, relu=True, drop_p=p1,
+                               seed=seed_fn())
+            head = hip_ops.deepfm_head(h, lw[:, D:].clone(), self.linear.bias, z_cross)
+            return head["p"].view(-1, 1)

@@ -10,7 +10,9 @@ of the checkpoint four epochs back.
 
 Differences, all deliberate: the training step is the fused HIP step (FM, DeepFM and
 IPNN; FFM: FusedFFMTrainer, the same deferred-exact Adam over its F*V field-table rows;
-AutogradTrainer keeps the autograd + torch.optim.Adam route for comparison; the other six model families are out of scope); the batches are
+FNN and DCN: AutogradTrainer, the reference's own step — autograd over the HIP kernels and
+torch.optim.Adam — which also serves the other models for comparison; LR, W&D, OPNN and AFM
+are out of scope); the batches are
 sliced from one device-resident copy of the data instead of 8 DataLoader worker
 processes; the rotating-checkpoint cleanup skips files that were never written (the
 reference crashes there when epoch < 5, all_main/pretrain_main.py:201-202).
@@ -52,9 +54,23 @@ def get_model(model_name, feature_nums, field_nums, latent_dims):
         return Model.InnerPNN(feature_nums, field_nums, latent_dims)
     if model_name == "FFM":
         return Model.FFM(feature_nums, field_nums, latent_dims)
+    if model_name == "FNN":
+        return Model.FNN(feature_nums, field_nums, latent_dims)
+    if model_name == "DCN":
+        return Model.DCN(feature_nums, field_nums, latent_dims)
     raise NotImplementedError(
-        f"{model_name}: FM, FFM, DeepFM and IPNN are built on HIP; "
-        "LR/W&D/FNN/OPNN/DCN/AFM are out of scope (SURVEY.md §2 row 7)")
+        f"{model_name}: FM, FFM, DeepFM, IPNN, FNN and DCN are built on HIP; "
+        "LR/W&D/OPNN/AFM are out of scope (SURVEY.md §2 row 7)")
+
+
+def make_trainer(model_name, model, learning_rate, weight_decay):
+    """The training step of a model family: the fused HIP step where one exists (FM, DeepFM,
+    IPNN; FFM), else the reference's own step through autograd (FNN, DCN)."""
+    if model_name == "FFM":
+        return FusedFFMTrainer(model, lr=learning_rate, weight_decay=weight_decay)
+    if model_name in ("FNN", "DCN"):
+        return AutogradTrainer(model, lr=learning_rate, weight_decay=weight_decay)
+    return FusedCTRTrainer(model, lr=learning_rate, weight_decay=weight_decay)
 
 
 class AutogradTrainer:
@@ -216,10 +232,7 @@ def main(data_path, dataset_name, campaign_id, latent_dims, model_name, epoch, l
 
     model = get_model(model_name, feature_nums, field_nums, latent_dims).to(device)
     loss = nn.BCELoss()
-    if model_name == "FFM":
-        trainer = FusedFFMTrainer(model, lr=learning_rate, weight_decay=weight_decay)
-    else:
-        trainer = FusedCTRTrainer(model, lr=learning_rate, weight_decay=weight_decay)
+    trainer = make_trainer(model_name, model, learning_rate, weight_decay)
 
     valid_aucs, valid_losses, history = [], [], []
     early_stop_index, is_early_stop = 0, False
@@ -280,7 +293,7 @@ def _parser():
     parser.add_argument("--data_path", default="../../data/")
     parser.add_argument("--dataset_name", default="avazu/", help="ipinyou, cretio, yoyi, avazu")
     parser.add_argument("--campaign_id", default="avazu/", help="1458, 3358, 3386, 3427, 3476, avazu")
-    parser.add_argument("--model_name", default="FM", help="FM, FFM, DeepFM, IPNN")
+    parser.add_argument("--model_name", default="FM", help="FM, FFM, DeepFM, IPNN, FNN, DCN")
     parser.add_argument("--latent_dims", type=int, default=10)
     parser.add_argument("--epoch", type=int, default=20)
     parser.add_argument("--learning_rate", type=float, default=1e-3)
