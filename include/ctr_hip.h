@@ -658,6 +658,53 @@ int ctr_dcn_cross_backward(int64_t B, int D, int L, const float* x0, int64_t ldx
                            float* dx0, int64_t ldd, float* dW, float* dbias, float* dw_tail,
                            void* ws, int64_t ws_bytes, ctr_stream_t stream);
 
+/* ------------------------------------- Prioritized replay memory (hybrid TD3, PER) ------
+ * The reference's Memory (Hybrid_TD3_model_PER.py:22-109) with storage and sampling on the
+ * device: memory [N, T] and prio [N] (the [N, 1] priority column) are fp32, contiguous, and
+ * written in place. No entry point copies to the host or waits for the device. N < 2^31.
+ * The priority of a TD error is (|td| + eps)^alpha in fp32 (get_priority).
+ * ctr_per_add: rows i = 0 .. n-1 of transitions [n, T] (row stride ldt) go to slot
+ *   (start + i) % N in one launch (0 <= start < N; the host never branches on wrap-around):
+ *   memory[slot] = transitions[i], prio[slot] = max(prio[slot], priority(td[i])) (a max,
+ *   not an overwrite: lines 53, 57, 61). n == 0 is a no-op; n > N is refused (two rows
+ *   would share a slot).
+ * ctr_per_update: prio[idx[i]] = priority(td[i]) for i < k (batch_update). An index outside
+ *   [0, N) is ignored. Duplicate indices are undefined (one of their values is kept), as in
+ *   the reference's indexed assignment.
+ * ctr_per_keys: the selection keys of elements [0, n_valid), bitwise the ones ctr_per_sample
+ *   orders by. An element with p <= 0 or a non-finite p has key -inf (picked last). Otherwise
+ *     mode 1 (greedy):      key_i = p_i
+ *     mode 0 (stochastic):  key_i = logf(p_i) + G_i, with
+ *       h = hash_u32(seed, i) (32 bits, csrc/ctr_common.h), all but its 24 leading
+ *       significant bits cleared; v = ((float)h + 0.5f) * 2^-32, exact, in [2^-33, 1 - 2^-24];
+ *       E = -log1pf(-v) in [2^-33, 16.7]; G_i = -logf(E) in [-2.9, 22.9] (Gumbel noise, finest
+ *       where G is large). Every key of a finite p > 0 is finite; a key of -0 is stored as +0.
+ *   The descending order of the top keys is, in distribution, the order of a sequential
+ *   weighted draw without replacement (np.random.choice(p=P, replace=False), line 72).
+ * ctr_per_sample: the k largest keys of [0, n_valid), 1 <= k <= min(n_valid, 8192), in
+ *   descending key order, ties to the lower index (so equal priorities under mode 1 come back
+ *   as the lowest slots, in order). Outputs idx [k] (int64), batch [k, T] = memory[idx] and
+ *   isw [k] = (prio[idx] / min_p)^(-beta), min_p = the smallest priority of [0, n_valid), also
+ *   stored to min_p[0] when given. Radix select over the order-preserving uint32 image of the
+ *   keys (computed once into ws, then three streaming passes with integer histograms), a
+ *   counting and a compaction pass with index-ordered slots (the ties taken are the lowest
+ *   indices), a rank sort in LDS, one gather. No float atomics: the same (prio, seed) gives
+ *   the same bits, order included. ws: ctr_per_workspace_bytes(N, k) bytes (4 N + about 100 KB),
+ *   16-byte aligned; the size does not depend on the fill level (0 for an N or k out of
+ *   range). */
+int64_t ctr_per_workspace_bytes(int64_t N, int k);
+int ctr_per_add(int64_t N, int T, int64_t start, int64_t n, const float* transitions,
+                int64_t ldt, const float* td, float eps, float alpha, float* memory,
+                float* prio, ctr_stream_t stream);
+int ctr_per_update(int64_t N, int64_t k, const int64_t* idx, const float* td, float eps,
+                   float alpha, float* prio, ctr_stream_t stream);
+int ctr_per_keys(int64_t n_valid, const float* prio, int mode, uint64_t seed, float* keys,
+                 ctr_stream_t stream);
+int ctr_per_sample(int64_t N, int T, int64_t n_valid, int k, int mode, uint64_t seed,
+                   float beta, const float* memory, const float* prio, int64_t* idx,
+                   float* batch, float* isw, float* min_p, void* ws, int64_t ws_bytes,
+                   ctr_stream_t stream);
+
 /* ------------------------------------------------------ A8: REINFORCE (PG) -----------
  * ctr_softmax_rows: out[b,:] = softmax(x[b,:]) (PG_model.py:56).
  * ctr_pg_discount_norm: discounted return of an episode, reverse recurrence

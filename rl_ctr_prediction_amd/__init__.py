@@ -1,6 +1,7 @@
 """MI355X-native CTR training hot path of jqsl2012/RL_CTR_Prediction.
 
-FM / FFM / DeepFM / InnerPNN / FNN / DCN / Feature_Embedding / PolicyGradient with the reference's construction API,
+FM / FFM / DeepFM / InnerPNN / FNN / DCN / Feature_Embedding / PolicyGradient / the prioritized replay Memory with the
+reference's construction API,
 running on hand-written gfx950 HIP kernels behind the C ABI in include/ctr_hip.h
 (libctr_hip.so). See DESIGN.md.
 """
@@ -9,8 +10,9 @@ from .ffm_trainer import FusedFFMTrainer
 from .optim import DenseAdam
 from .p_model import DCN, FFM, FM, FNN, DeepFM, InnerPNN
 from .pg_model import Net, PolicyGradient
+from .replay_memory import Memory as PrioritizedMemory
 from .sharded import ShardedCTRTrainer
 from .trainer import FusedCTRTrainer
 
 __all__ = ["FM", "FFM", "DeepFM", "InnerPNN", "FNN", "DCN", "Feature_Embedding", "Net", "PolicyGradient", "FusedCTRTrainer",
-           "FusedFFMTrainer", "ShardedCTRTrainer", "DenseAdam"]
+           "FusedFFMTrainer", "ShardedCTRTrainer", "DenseAdam", "PrioritizedMemory"]

@@ -231,6 +231,12 @@ SIGNATURES = {
                                      _vp, _vp]),
     "ctr_dcn_cross_backward": (_i32, [_i64, _i32, _i32, _vp, _i64, _vp, _vp, _vp, _vp, _i64, _vp,
                                       _vp, _vp, _i64, _vp, _vp, _vp, _vp, _i64, _vp]),
+    "ctr_per_workspace_bytes": (_i64, [_i64, _i32]),
+    "ctr_per_add": (_i32, [_i64, _i32, _i64, _i64, _vp, _i64, _vp, _f32, _f32, _vp, _vp, _vp]),
+    "ctr_per_update": (_i32, [_i64, _i64, _vp, _vp, _f32, _f32, _vp, _vp]),
+    "ctr_per_keys": (_i32, [_i64, _vp, _i32, _u64, _vp, _vp]),
+    "ctr_per_sample": (_i32, [_i64, _i32, _i64, _i32, _i32, _u64, _f32, _vp, _vp, _vp, _vp, _vp,
+                              _vp, _vp, _i64, _vp]),
     "ctr_softmax_rows": (_i32, [_vp, _i64, _i32, _vp, _vp]),
     "ctr_pg_workspace_bytes": (_i64, [_i64]),
     "ctr_pg_discount_norm": (_i32, [_vp, _i64, _f64, _vp, _vp, _vp, _vp, _i64, _vp]),

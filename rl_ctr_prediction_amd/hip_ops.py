@@ -24,6 +24,7 @@ __all__ = [
     "fm_embedding_grad_adam", "segment_sum_rows_adam",
     "rows_to_dense", "adam_dense", "fm_step_tail", "adam_embedding", "adam_scalars", "feature_embedding",
     "dcn_cross_forward", "dcn_cross_backward",
+    "per_add", "per_update", "per_keys", "per_sample", "PER_STOCHASTIC", "PER_GREEDY", "PER_MAX_K",
     "AdamStepTable", "adam_deferred_rows", "adam_deferred_flush", "adam_deferred_catchup_ids",
     "step_begin", "step_end", "ids_add_", "shard_pack_ids", "shard_runs_copy",
     "softmax_rows", "pg_discount_norm", "pg_loss_grad", "pg_vt_mean", "pg_loss_grad_global", "check_index_error", "Workspace",
@@ -1187,6 +1188,102 @@ def dcn_cross_backward(x0: torch.Tensor, W: torch.Tensor, bias: torch.Tensor, s:
                                _p(w_tail), _p(dx0), dx0.stride(0) if B else D, _p(out["dW"]),
                                _p(out["dbias"]), _p(out.get("dw_tail")), _p(ws), ws.numel(),
                                _stream())
+    return out
+
+
+# ------------------------------------------------- prioritized replay memory (PER) ----
+PER_STOCHASTIC, PER_GREEDY = 0, 1
+PER_MAX_K = 8192
+_per_ws: dict = {}  # (device index, stream, N, k) -> scratch of ctr_per_workspace_bytes(N, k)
+
+
+def _per_store(memory: torch.Tensor, prio: torch.Tensor) -> tuple[int, int]:
+    _f32(memory, "memory")
+    _f32(prio, "prio")
+    if memory.dim() != 2 or prio.numel() != memory.shape[0]:
+        raise ValueError("per: memory must be [N, T] and prio must hold N priorities")
+    return memory.shape[0], memory.shape[1]
+
+
+def _per_td(td: torch.Tensor, n: int) -> torch.Tensor:
+    _f32(td, "td")
+    if td.numel() != n:
+        raise ValueError(f"per: td must hold {n} errors, got {tuple(td.shape)}")
+    return td
+
+
+def per_add(memory: torch.Tensor, prio: torch.Tensor, start: int, transitions: torch.Tensor,
+            td: torch.Tensor, eps: float, alpha: float) -> None:
+    """Memory.add's writes (Hybrid_TD3_model_PER.py:44-63): transitions [n, T] go to slots
+    (start + i) % N of memory [N, T]; prio = max(prio, (|td| + eps)^alpha) there. One launch."""
+    N, T = _per_store(memory, prio)
+    n = transitions.shape[0] if transitions.dim() == 2 else -1
+    if n < 0 or transitions.shape[1] != T:
+        raise ValueError(f"per_add: transitions must be [n, {T}]")
+    _rows2d(transitions, "transitions", n, T)
+    _per_td(td, n)
+    lib.ctr_per_add(N, T, start, n, _p(transitions), transitions.stride(0) if n else T, _p(td),
+                    eps, alpha, _p(memory), _p(prio), _stream())
+
+
+def per_update(prio: torch.Tensor, idx: torch.Tensor, td: torch.Tensor, eps: float,
+               alpha: float) -> None:
+    """Memory.batch_update: prio[idx] = (|td| + eps)^alpha (duplicate indices: undefined)."""
+    _f32(prio, "prio")
+    _dev(idx, "idx")
+    if idx.dtype != torch.int64 or idx.dim() != 1 or not idx.is_contiguous():
+        raise ValueError("per_update: idx must be a contiguous int64 vector")
+    _per_td(td, idx.numel())
+    lib.ctr_per_update(prio.numel(), idx.numel(), _p(idx), _p(td), eps, alpha, _p(prio),
+                       _stream())
+
+
+def per_keys(prio: torch.Tensor, n_valid: int, mode: int, seed: int,
+             out: torch.Tensor | None = None) -> torch.Tensor:
+    """The selection keys of prio[:n_valid] (include/ctr_hip.h), bitwise what per_sample
+    orders by."""
+    _f32(prio, "prio")
+    if not 0 <= n_valid <= prio.numel():
+        raise ValueError(f"per_keys: n_valid {n_valid} outside [0, {prio.numel()}]")
+    if out is None:
+        out = torch.empty(n_valid, dtype=torch.float32, device=prio.device)
+    _f32(out, "keys")
+    if out.numel() < n_valid:
+        raise ValueError("per_keys: out is shorter than n_valid")
+    lib.ctr_per_keys(n_valid, _p(prio), mode, seed, _p(out), _stream())
+    return out
+
+
+def per_sample(memory: torch.Tensor, prio: torch.Tensor, n_valid: int, k: int, mode: int,
+               seed: int, beta: float, out: dict | None = None) -> dict:
+    """The k largest selection keys of the filled prefix [0, n_valid), in descending order:
+    dict(idx [k] int64, batch [k, T] = memory[idx], isw [k, 1] = (prio[idx] / min_p)^(-beta),
+    min_p [1]). mode PER_STOCHASTIC draws by priority without replacement (seed picks the
+    draw), PER_GREEDY takes the largest priorities. Nothing is copied to the host."""
+    N, T = _per_store(memory, prio)
+    if not 1 <= k <= min(n_valid, PER_MAX_K) or n_valid > N:
+        raise ValueError(f"per_sample: k={k} outside [1, min(n_valid={n_valid}, {PER_MAX_K})] "
+                         f"or n_valid > N={N}")
+    dev = memory.device
+    if out is None:
+        out = dict(idx=torch.empty(k, dtype=torch.int64, device=dev),
+                   batch=torch.empty(k, T, dtype=torch.float32, device=dev),
+                   isw=torch.empty(k, 1, dtype=torch.float32, device=dev),
+                   min_p=torch.empty(1, dtype=torch.float32, device=dev))
+    idx, batch, isw, min_p = _dev(out["idx"], "idx"), _f32(out["batch"], "batch"), \
+        _f32(out["isw"], "isw"), out.get("min_p")
+    if (idx.dtype != torch.int64 or not idx.is_contiguous() or idx.numel() != k
+            or batch.numel() != k * T or isw.numel() != k):
+        raise ValueError(f"per_sample: out must hold idx [{k}] int64, batch [{k}, {T}], isw [{k}]")
+    if min_p is not None:
+        _f32(min_p, "min_p")
+    key = (dev.index, _stream(), N, k)  # launches on one stream are ordered: they may share it
+    ws = _per_ws.get(key)
+    if ws is None:
+        ws = _per_ws[key] = torch.empty(lib.ctr_per_workspace_bytes(N, k), dtype=torch.uint8,
+                                        device=dev)
+    lib.ctr_per_sample(N, T, n_valid, k, mode, seed, beta, _p(memory), _p(prio), _p(idx),
+                       _p(batch), _p(isw), _p(min_p), _p(ws), ws.numel(), _stream())
     return out
 
 
