@@ -68,7 +68,8 @@ int ctr_stream_create_cu_masked(const uint32_t* mask, int n_words, ctr_stream_t*
 int ctr_stream_destroy(ctr_stream_t stream);
 
 /* ---------------------------------------------------------------- A3: gather ---------
- * out[i, :] = table[idx[i], :]  — nn.Embedding.forward.
+ * out[i, :] = table[idx[i], :]  — nn.Embedding.forward. n = 0 is a no-op (idx and out may
+ * be NULL: an empty tensor has no storage).
  * Replaces: p_model.py:47,303,320 and Feature_embedding.py:52 (self.feature_embedding(x)). */
 int ctr_embedding_gather(const float* table, int64_t V, int K, const void* idx, int idx_type,
                          int64_t n, float* out, int32_t* err_flag, ctr_stream_t stream);

@@ -366,9 +366,10 @@ using namespace ctr;
 extern "C" int ctr_embedding_gather(const float* table, int64_t V, int K, const void* idx,
                                     int idx_type, int64_t n, float* out, int32_t* err_flag,
                                     ctr_stream_t stream) {
-  CTR_REQUIRE(table && idx && out, "ctr_embedding_gather: null pointer");
   CTR_REQUIRE(V > 0 && K > 0 && n >= 0, "ctr_embedding_gather: bad sizes V=%lld K=%d n=%lld",
               (long long)V, K, (long long)n);
+  // an empty batch has no id / output storage (torch gives a 0-element tensor a null pointer)
+  CTR_REQUIRE(table && (n == 0 || (idx && out)), "ctr_embedding_gather: null pointer");
   CTR_REQUIRE(idx_type == CTR_IDX_I32 || idx_type == CTR_IDX_I64, "bad idx_type %d", idx_type);
   if (n == 0) return CTR_OK;
   hipStream_t st = as_stream(stream);

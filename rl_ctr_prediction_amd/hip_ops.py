@@ -16,7 +16,7 @@ import torch
 
 from ._lib import (CTR_EFLAG_CAPACITY, CTR_EFLAG_INDEX, CTR_IDX_I32, CTR_IDX_I64, EPI_BIAS, EPI_BIAS_RELU,
                    EPI_BIAS_RELU_DROP, EPI_GRAD_MASK, EPI_NONE, PlanesDesc, PlaneViewDesc, SparsePlan,
-                   lib)
+                   CtrHipError, lib)
 
 __all__ = [
     "embedding_gather", "fm_forward", "fm_forward_planes", "bce_sigmoid", "deepfm_head", "gemm", "linear",
@@ -49,6 +49,24 @@ def _f32(t: torch.Tensor, name: str) -> torch.Tensor:
     if not t.is_contiguous():
         raise ValueError(f"{name}: must be contiguous")
     return t
+
+
+def _f32_rows(t: torch.Tensor, name: str) -> int:
+    """A float32 [M, N] device matrix whose rows are contiguous (a column slice of a wider
+    matrix is fine); returns its leading dimension."""
+    _dev(t, name)
+    if t.dtype != torch.float32:
+        raise TypeError(f"{name}: expected float32, got {t.dtype}")
+    M, N = t.shape
+    if t.numel() == 0:
+        return max(N, 1)
+    if N > 1 and t.stride(1) != 1:
+        raise ValueError(f"{name}: rows must be contiguous")
+    if M == 1:  # a single row's stride is arbitrary (torch keeps any value)
+        return N
+    if t.stride(0) < N:
+        raise ValueError(f"{name}: row stride {t.stride(0)} < N = {N}")
+    return t.stride(0)
 
 
 def _p(t):
@@ -429,23 +447,26 @@ def colsum_multi(jobs) -> None:
     for i, job in enumerate(jobs):
         X, row_w, out = job[:3]
         scale = float(job[3]) if len(job) > 3 else 1.0
-        _f32(X, "X")
         if X.dim() != 2 or out.numel() != X.shape[1]:
             raise ValueError("colsum_multi: X must be [M, N] and out N elements")
-        arr[i] = ColsumJob(_p(X), X.shape[0], X.shape[1], X.stride(0), _p(row_w), scale, _p(out))
+        ldx = _f32_rows(X, "X")
+        arr[i] = ColsumJob(_p(X), X.shape[0], X.shape[1], ldx, _p(row_w), scale, _p(out))
     nbytes = lib.ctr_colsum_multi_workspace_bytes(len(jobs), arr)
+    if nbytes < 0:  # refused (job count, a bad job): nothing is launched
+        raise CtrHipError("ctr_colsum_multi_workspace_bytes failed: "
+                          + lib.ctr_last_error().decode(errors="replace"))
     ws = Workspace.get(nbytes, jobs[0][0].device)
     lib.ctr_colsum_multi_f32(len(jobs), arr, _p(ws), ws.numel(), _stream())
 
 
 def colsum(X: torch.Tensor, row_w: torch.Tensor | None = None, scale: float = 1.0,
            out=None) -> torch.Tensor:
-    _f32(X, "X")
+    ldx = _f32_rows(X, "X")
     M, N = X.shape
     if out is None:
         out = torch.empty(N, dtype=torch.float32, device=X.device)
     ws = Workspace.get(lib.ctr_reduce_workspace_bytes(M, N), X.device)
-    lib.ctr_colsum_f32(_p(X), M, N, X.stride(0), _p(row_w), float(scale), _p(out), _p(ws),
+    lib.ctr_colsum_f32(_p(X), M, N, ldx, _p(row_w), float(scale), _p(out), _p(ws),
                        ws.numel(), _stream())
     return out
 

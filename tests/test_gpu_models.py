@@ -613,9 +613,20 @@ def test_autograd_ffm_two_adam_steps_vs_reference(cuda, golden):
 
 
 @pytest.mark.parametrize("V,F,K,B", [(100_000, 26, 16, 1024), (50, 3, 1, 7), (2000, 39, 10, 300),
-                                     (500, 5, 64, 40)])
+                                     (500, 5, 64, 40), (60, 5, 48, 9), (300, 6, 64, 67)])
 def test_ffm_grads_vs_oracle(cuda, V, F, K, B):
-    """Criteo-shape and edge FFM shapes: forward and every table's gradient vs the oracle."""
+    """Criteo-shape and edge FFM shapes (K = 48: one pair group with 16 idle lanes; K = 64:
+    none): forward and every table's gradient vs the oracle."""
+    _ffm_grads_case(cuda, V, F, K, B, torch.int64)
+
+
+@pytest.mark.parametrize("V,F,K,B", [(60, 5, 48, 9), (300, 6, 64, 67)])
+def test_ffm_grads_vs_oracle_int32(cuda, V, F, K, B):
+    """The same with int32 feature ids (the kernels' other id type)."""
+    _ffm_grads_case(cuda, V, F, K, B, torch.int32)
+
+
+def _ffm_grads_case(cuda, V, F, K, B, dtype):
     P = _pkg()
     from rl_ctr_prediction_amd.synthetic import CriteoSynth
     torch.manual_seed(V + F)
@@ -632,7 +643,7 @@ def test_ffm_grads_vs_oracle(cuda, V, F, K, B):
         y = (torch.rand(B, 1) < 0.3).float()
     params = {k: v.detach().cpu().clone().requires_grad_(True) for k, v in m.state_dict().items()}
     lref, pref, gref = O.grads("FFM", params, x, y)
-    p = m(x.to(cuda))
+    p = m(x.to(dtype).to(cuda))
     np.testing.assert_allclose(p.detach().cpu().numpy(), pref.numpy(), rtol=1e-5, atol=1e-6)
     loss = torch.nn.BCELoss()(p, y.to(cuda))
     m.zero_grad()
