@@ -706,6 +706,85 @@ int ctr_per_sample(int64_t N, int T, int64_t n_valid, int k, int mode, uint64_t 
                    float* batch, float* isw, float* min_p, void* ws, int64_t ws_bytes,
                    ctr_stream_t stream);
 
+/* ------------------------------------------- Hybrid TD3 agent (actor, twin critics) -----
+ * The small kernels of Critic, hybrid_actors and Hybrid_TD3_Model.learn
+ * (Hybrid_TD3_model_PER.py:111-393); the Linear layers run on ctr_gemm_f32_ex. All fp32, no
+ * float atomics, every sum in an order fixed by the sizes: the same inputs give the same bits.
+ * ctr_bn_forward, ctr_bn_backward and ctr_soft_update_multi use 16-byte accesses when N (or
+ * numel), every row stride and every pointer allow them and scalar ones otherwise; the noise,
+ * action-head, smoothing and critic-loss kernels (A <= 64 columns, [B] vectors) are scalar.
+ * B < 2^31.
+ * ctr_bn_forward: nn.BatchNorm1d on x [B, N] (row stride ldx) -> y (row stride ldy, so y may
+ *   be a column block of a wider matrix), then ReLU when relu != 0.
+ *   training != 0: per-column mean and biased variance over the B >= 2 rows (B < 2 is refused,
+ *     as torch refuses it), two passes with fp64 accumulators, never E[x^2] - E[x]^2;
+ *     invstd = 1 / sqrt(var + eps); y = (x - mean) * invstd * gamma + beta, evaluated in fp64
+ *     and rounded once. save_mean, save_invstd [N] (optional) are what ctr_bn_backward needs;
+ *     save_mean_lo, save_invstd_lo [N] (optional) are the parts of the fp64 mean and invstd
+ *     that their fp32 values drop (with few rows dx's terms cancel almost entirely, and the
+ *     backward, given them, loses nothing to that rounding). running_mean / running_var (both or neither) are updated in
+ *     place: rm = (1 - momentum) * rm + momentum * mean, rv likewise with the unbiased
+ *     variance var * B / (B - 1).
+ *   training == 0: y = (x - running_mean) / sqrt(running_var + eps) * gamma + beta, row-local,
+ *     any B >= 1; nothing but y is written.
+ * ctr_bn_backward: the training-mode backward from dy (row stride lddy), x and the saved
+ *   statistics. With relu != 0, dy is first masked by y > 0 (y: the forward's output, row
+ *   stride ldy). dbeta = sum g, dgamma = sum g * x_hat, and, unless dx is NULL,
+ *   dx = gamma * invstd * (g - dbeta / B - x_hat * dgamma / B) (row stride ldd), in one launch,
+ *   in fp64 rounded once; save_mean_lo and save_invstd_lo may be NULL (taken as 0).
+ *   The eval-mode backward is not provided.
+ * ctr_td3_noise: out[i] = z(seed, offset + i), i < n, unit normal by Box-Muller from a
+ *   stateless hash: h1 = hash_u32(seed, 2e), h2 = hash_u32(seed, 2e + 1) (csrc/ctr_common.h),
+ *   u = ((float)(h >> 8) + 0.5f) * 2^-24 in (0, 1), z = sqrtf(-2 logf(u1)) * cosf(2 pi u2),
+ *   |z| < 5.9. ctr_td3_act and ctr_td3_smooth in noise_mode 2 use element B * A * head + row *
+ *   A + col of stream `seed` (head 0: continuous, 1: discrete) through the same device
+ *   function: ctr_td3_noise(B * A, seed, head * B * A) returns the bits they consumed.
+ * ctr_td3_act: the two action heads of hybrid_actors from their pre-activations pre_c, pre_d
+ *   [B, A] (row stride ldp), A <= 64. c = tanh(pre_c), d = tanh(pre_d); with noise_mode 1
+ *   (noise_c, noise_d [B, A] contiguous) or 2 (seed), v = clamp(v + noise * sigma, -1, 1)
+ *   (lines 234, 238); noise_mode 0 is tanh only (evaluate). Outputs c_actions, d_actions
+ *   [B, A], and optionally c_softmax = softmax(c_actions) [B, A] and d_index [B] (int64) =
+ *   argmax(d_actions) + 1, the LOWEST index among equal values (argsort(-d)[:, 0] + 1).
+ * ctr_td3_smooth: target policy smoothing (lines 354-355) of both heads:
+ *   out = clamp(mean + clamp(0.2 * noise, -0.5, 0.5), -1, 1), mean [B, A] (row stride ldm;
+ *   apply_tanh != 0: the means are pre-activations, tanh is applied first), out with row stride
+ *   ldo: two column blocks of the target critic's input. noise_mode 1 or 2 as above.
+ * ctr_td3_critic_loss: from q1, q2, q1_t, q2_t, isw [B] and r (stride ldr: a column of the
+ *   sampled batch): q_target = r + gamma * min(q1_t, q2_t); td = 2 q_target - q1 - q2;
+ *   loss[0] = mean(isw * ((q1 - q_target)^2 + (q2 - q_target)^2)); dq = 2 isw (q - q_target) / B.
+ *   One block, fixed order.
+ * ctr_soft_update_multi: target = target * (1 - tau) + source * tau for `count` (<= 4096)
+ *   tensors in one launch; table is a DEVICE array of count entries, max_numel the largest
+ *   numel in it (it sizes the grid). (float)(1.0 - tau) and (float)tau multiply in fp32, each
+ *   product rounded before the sum, as line 335 evaluates. */
+typedef struct ctr_soft_update_entry {
+  float* target; const float* source; int64_t numel;
+} ctr_soft_update_entry;
+int ctr_bn_forward(int64_t B, int N, const float* x, int64_t ldx, const float* gamma,
+                   const float* beta, float* running_mean, float* running_var, float eps,
+                   float momentum, int training, int relu, float* y, int64_t ldy,
+                   float* save_mean, float* save_mean_lo, float* save_invstd,
+                   float* save_invstd_lo, ctr_stream_t stream);
+int ctr_bn_backward(int64_t B, int N, const float* dy, int64_t lddy, const float* y,
+                    int64_t ldy, int relu, const float* x, int64_t ldx, const float* save_mean,
+                    const float* save_mean_lo, const float* save_invstd,
+                    const float* save_invstd_lo, const float* gamma, float* dgamma, float* dbeta,
+                    float* dx, int64_t ldd, ctr_stream_t stream);
+int ctr_td3_noise(int64_t n, uint64_t seed, uint64_t offset, float* out, ctr_stream_t stream);
+int ctr_td3_act(int64_t B, int A, const float* pre_c, const float* pre_d, int64_t ldp,
+                int noise_mode, const float* noise_c, const float* noise_d, uint64_t seed,
+                float sigma, float* c_actions, float* c_softmax, float* d_actions,
+                int64_t* d_index, ctr_stream_t stream);
+int ctr_td3_smooth(int64_t B, int A, const float* mean_c, const float* mean_d, int64_t ldm,
+                   int apply_tanh, int noise_mode, const float* noise_c, const float* noise_d,
+                   uint64_t seed, float* out_c, float* out_d, int64_t ldo, ctr_stream_t stream);
+int ctr_td3_critic_loss(int64_t B, const float* q1, const float* q2, const float* q1_t,
+                        const float* q2_t, const float* r, int64_t ldr, const float* isw,
+                        float gamma, float* q_target, float* td, float* loss, float* dq1,
+                        float* dq2, ctr_stream_t stream);
+int ctr_soft_update_multi(int count, const ctr_soft_update_entry* table, int64_t max_numel,
+                          double tau, ctr_stream_t stream);
+
 /* ------------------------------------------------------ A8: REINFORCE (PG) -----------
  * ctr_softmax_rows: out[b,:] = softmax(x[b,:]) (PG_model.py:56).
  * ctr_pg_discount_norm: discounted return of an episode, reverse recurrence
@@ -830,6 +909,55 @@ typedef struct ctr_pg_returns_args {
   void* ws; int64_t ws_bytes; int flags;
 } ctr_pg_returns_args;
 int ctr_op_pg_returns(const ctr_pg_returns_args* a, ctr_stream_t stream);
+
+/* The hybrid TD3 agent's operations in struct form: each forwards its fields to the flat entry
+ * point of the same name (see there for the semantics). None needs scratch. */
+typedef struct ctr_bn_forward_args {
+  int64_t B; int N; const float* x; int64_t ldx; const float* gamma; const float* beta;
+  float* running_mean; float* running_var; float eps; float momentum; int training; int relu;
+  float* y; int64_t ldy; float* save_mean; float* save_mean_lo; float* save_invstd;
+  float* save_invstd_lo;
+} ctr_bn_forward_args;
+int ctr_op_bn_forward(const ctr_bn_forward_args* a, ctr_stream_t stream);
+
+typedef struct ctr_bn_backward_args {
+  int64_t B; int N; const float* dy; int64_t lddy; const float* y; int64_t ldy; int relu;
+  const float* x; int64_t ldx; const float* save_mean; const float* save_mean_lo;
+  const float* save_invstd; const float* save_invstd_lo; const float* gamma; float* dgamma;
+  float* dbeta; float* dx; int64_t ldd;
+} ctr_bn_backward_args;
+int ctr_op_bn_backward(const ctr_bn_backward_args* a, ctr_stream_t stream);
+
+typedef struct ctr_td3_noise_args {
+  int64_t n; uint64_t seed; uint64_t offset; float* out;
+} ctr_td3_noise_args;
+int ctr_op_td3_noise(const ctr_td3_noise_args* a, ctr_stream_t stream);
+
+typedef struct ctr_td3_act_args {
+  int64_t B; int A; const float* pre_c; const float* pre_d; int64_t ldp; int noise_mode;
+  const float* noise_c; const float* noise_d; uint64_t seed; float sigma;
+  float* c_actions; float* c_softmax; float* d_actions; int64_t* d_index;
+} ctr_td3_act_args;
+int ctr_op_td3_act(const ctr_td3_act_args* a, ctr_stream_t stream);
+
+typedef struct ctr_td3_smooth_args {
+  int64_t B; int A; const float* mean_c; const float* mean_d; int64_t ldm; int apply_tanh;
+  int noise_mode; const float* noise_c; const float* noise_d; uint64_t seed;
+  float* out_c; float* out_d; int64_t ldo;
+} ctr_td3_smooth_args;
+int ctr_op_td3_smooth(const ctr_td3_smooth_args* a, ctr_stream_t stream);
+
+typedef struct ctr_td3_critic_loss_args {
+  int64_t B; const float* q1; const float* q2; const float* q1_t; const float* q2_t;
+  const float* r; int64_t ldr; const float* isw; float gamma;
+  float* q_target; float* td; float* loss; float* dq1; float* dq2;
+} ctr_td3_critic_loss_args;
+int ctr_op_td3_critic_loss(const ctr_td3_critic_loss_args* a, ctr_stream_t stream);
+
+typedef struct ctr_soft_update_multi_args {
+  int count; const ctr_soft_update_entry* table; int64_t max_numel; double tau;
+} ctr_soft_update_multi_args;
+int ctr_op_soft_update_multi(const ctr_soft_update_multi_args* a, ctr_stream_t stream);
 
 #ifdef __cplusplus
 }

@@ -1,12 +1,14 @@
 """MI355X-native CTR training hot path of jqsl2012/RL_CTR_Prediction.
 
-FM / FFM / DeepFM / InnerPNN / FNN / DCN / Feature_Embedding / PolicyGradient / the prioritized replay Memory with the
+FM / FFM / DeepFM / InnerPNN / FNN / DCN / Feature_Embedding / PolicyGradient / the hybrid TD3
+agent (Hybrid_TD3_Model, Critic, hybrid_actors) and its prioritized replay Memory with the
 reference's construction API,
 running on hand-written gfx950 HIP kernels behind the C ABI in include/ctr_hip.h
 (libctr_hip.so). See DESIGN.md.
 """
 from .feature_embedding import Feature_Embedding
 from .ffm_trainer import FusedFFMTrainer
+from .hybrid_td3_model_per import Critic, Hybrid_TD3_Model, hybrid_actors
 from .optim import DenseAdam
 from .p_model import DCN, FFM, FM, FNN, DeepFM, InnerPNN
 from .pg_model import Net, PolicyGradient
@@ -15,4 +17,5 @@ from .sharded import ShardedCTRTrainer
 from .trainer import FusedCTRTrainer
 
 __all__ = ["FM", "FFM", "DeepFM", "InnerPNN", "FNN", "DCN", "Feature_Embedding", "Net", "PolicyGradient", "FusedCTRTrainer",
-           "FusedFFMTrainer", "ShardedCTRTrainer", "DenseAdam", "PrioritizedMemory"]
+           "FusedFFMTrainer", "ShardedCTRTrainer", "DenseAdam", "PrioritizedMemory",
+           "Hybrid_TD3_Model", "Critic", "hybrid_actors"]

@@ -113,10 +113,60 @@ class PgReturnsArgs(C.Structure):
                 ("ws", _vp), ("ws_bytes", _i64), ("flags", _i32)]
 
 
+class SoftUpdateEntry(C.Structure):
+    """Mirror of ``ctr_soft_update_entry`` (include/ctr_hip.h): three 8-byte words."""
+    _fields_ = [("target", _vp), ("source", _vp), ("numel", _i64)]
+
+
+class BnForwardArgs(C.Structure):
+    _fields_ = [("B", _i64), ("N", _i32), ("x", _vp), ("ldx", _i64), ("gamma", _vp),
+                ("beta", _vp), ("running_mean", _vp), ("running_var", _vp), ("eps", _f32),
+                ("momentum", _f32), ("training", _i32), ("relu", _i32), ("y", _vp),
+                ("ldy", _i64), ("save_mean", _vp), ("save_mean_lo", _vp), ("save_invstd", _vp),
+                ("save_invstd_lo", _vp)]
+
+
+class BnBackwardArgs(C.Structure):
+    _fields_ = [("B", _i64), ("N", _i32), ("dy", _vp), ("lddy", _i64), ("y", _vp),
+                ("ldy", _i64), ("relu", _i32), ("x", _vp), ("ldx", _i64), ("save_mean", _vp),
+                ("save_mean_lo", _vp), ("save_invstd", _vp), ("save_invstd_lo", _vp),
+                ("gamma", _vp), ("dgamma", _vp), ("dbeta", _vp), ("dx", _vp), ("ldd", _i64)]
+
+
+class Td3NoiseArgs(C.Structure):
+    _fields_ = [("n", _i64), ("seed", _u64), ("offset", _u64), ("out", _vp)]
+
+
+class Td3ActArgs(C.Structure):
+    _fields_ = [("B", _i64), ("A", _i32), ("pre_c", _vp), ("pre_d", _vp), ("ldp", _i64),
+                ("noise_mode", _i32), ("noise_c", _vp), ("noise_d", _vp), ("seed", _u64),
+                ("sigma", _f32), ("c_actions", _vp), ("c_softmax", _vp), ("d_actions", _vp),
+                ("d_index", _vp)]
+
+
+class Td3SmoothArgs(C.Structure):
+    _fields_ = [("B", _i64), ("A", _i32), ("mean_c", _vp), ("mean_d", _vp), ("ldm", _i64),
+                ("apply_tanh", _i32), ("noise_mode", _i32), ("noise_c", _vp), ("noise_d", _vp),
+                ("seed", _u64), ("out_c", _vp), ("out_d", _vp), ("ldo", _i64)]
+
+
+class Td3CriticLossArgs(C.Structure):
+    _fields_ = [("B", _i64), ("q1", _vp), ("q2", _vp), ("q1_t", _vp), ("q2_t", _vp), ("r", _vp),
+                ("ldr", _i64), ("isw", _vp), ("gamma", _f32), ("q_target", _vp), ("td", _vp),
+                ("loss", _vp), ("dq1", _vp), ("dq2", _vp)]
+
+
+class SoftUpdateMultiArgs(C.Structure):
+    _fields_ = [("count", _i32), ("table", _vp), ("max_numel", _i64), ("tau", _f64)]
+
+
 OP_ARGS = {"fm_fwd": FmFwdArgs, "fm_bwd": FmBwdArgs, "deepfm_gather_concat": DeepfmGatherConcatArgs,
            "emb_scatter_add": EmbScatterAddArgs, "adam_dense": AdamDenseArgs,
            "adam_rowwise": AdamRowwiseArgs, "pairwise_fe": PairwiseFeArgs,
-           "pg_returns": PgReturnsArgs}
+           "pg_returns": PgReturnsArgs, "bn_forward": BnForwardArgs,
+           "bn_backward": BnBackwardArgs, "td3_noise": Td3NoiseArgs, "td3_act": Td3ActArgs,
+           "td3_smooth": Td3SmoothArgs, "td3_critic_loss": Td3CriticLossArgs,
+           "soft_update_multi": SoftUpdateMultiArgs}
 
 
 # name -> (restype, argtypes); the list is the whole ABI and tests/test_abi.py checks it
@@ -237,6 +287,18 @@ SIGNATURES = {
     "ctr_per_keys": (_i32, [_i64, _vp, _i32, _u64, _vp, _vp]),
     "ctr_per_sample": (_i32, [_i64, _i32, _i64, _i32, _i32, _u64, _f32, _vp, _vp, _vp, _vp, _vp,
                               _vp, _vp, _i64, _vp]),
+    "ctr_bn_forward": (_i32, [_i64, _i32, _vp, _i64, _vp, _vp, _vp, _vp, _f32, _f32, _i32, _i32,
+                              _vp, _i64, _vp, _vp, _vp, _vp, _vp]),
+    "ctr_bn_backward": (_i32, [_i64, _i32, _vp, _i64, _vp, _i64, _i32, _vp, _i64, _vp, _vp, _vp,
+                               _vp, _vp, _vp, _vp, _vp, _i64, _vp]),
+    "ctr_td3_noise": (_i32, [_i64, _u64, _u64, _vp, _vp]),
+    "ctr_td3_act": (_i32, [_i64, _i32, _vp, _vp, _i64, _i32, _vp, _vp, _u64, _f32, _vp, _vp, _vp,
+                           _vp, _vp]),
+    "ctr_td3_smooth": (_i32, [_i64, _i32, _vp, _vp, _i64, _i32, _i32, _vp, _vp, _u64, _vp, _vp,
+                              _i64, _vp]),
+    "ctr_td3_critic_loss": (_i32, [_i64, _vp, _vp, _vp, _vp, _vp, _i64, _vp, _f32, _vp, _vp, _vp,
+                                   _vp, _vp, _vp]),
+    "ctr_soft_update_multi": (_i32, [_i32, _vp, _i64, _f64, _vp]),
     "ctr_softmax_rows": (_i32, [_vp, _i64, _i32, _vp, _vp]),
     "ctr_pg_workspace_bytes": (_i64, [_i64]),
     "ctr_pg_discount_norm": (_i32, [_vp, _i64, _f64, _vp, _vp, _vp, _vp, _i64, _vp]),

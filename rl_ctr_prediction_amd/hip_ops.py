@@ -25,6 +25,9 @@ __all__ = [
     "rows_to_dense", "adam_dense", "fm_step_tail", "adam_embedding", "adam_scalars", "feature_embedding",
     "dcn_cross_forward", "dcn_cross_backward",
     "per_add", "per_update", "per_keys", "per_sample", "PER_STOCHASTIC", "PER_GREEDY", "PER_MAX_K",
+    "bn_forward", "bn_backward", "td3_noise", "td3_act", "td3_smooth", "td3_critic_loss",
+    "SoftUpdateTable", "soft_update_multi", "TD3_NOISE_NONE", "TD3_NOISE_PTR", "TD3_NOISE_SEED",
+    "TD3_MAX_A",
     "AdamStepTable", "adam_deferred_rows", "adam_deferred_flush", "adam_deferred_catchup_ids",
     "step_begin", "step_end", "ids_add_", "shard_pack_ids", "shard_runs_copy",
     "softmax_rows", "pg_discount_norm", "pg_loss_grad", "pg_vt_mean", "pg_loss_grad_global", "check_index_error", "Workspace",
@@ -1306,6 +1309,216 @@ def per_sample(memory: torch.Tensor, prio: torch.Tensor, n_valid: int, k: int, m
     lib.ctr_per_sample(N, T, n_valid, k, mode, seed, beta, _p(memory), _p(prio), _p(idx),
                        _p(batch), _p(isw), _p(min_p), _p(ws), ws.numel(), _stream())
     return out
+
+
+# --------------------------------------------- hybrid TD3 agent (csrc/td3.hip) ---------
+TD3_NOISE_NONE, TD3_NOISE_PTR, TD3_NOISE_SEED = 0, 1, 2
+TD3_MAX_A = 64
+
+
+def _ld2(t: torch.Tensor, name: str) -> int:
+    """A float32 [B, N] device matrix with unit column stride (a column block of a wider
+    matrix is fine); returns its row stride."""
+    _dev(t, name)
+    if t.dtype != torch.float32 or t.dim() != 2:
+        raise TypeError(f"{name}: expected a float32 matrix, got {t.dtype} {tuple(t.shape)}")
+    B, N = t.shape
+    if N > 1 and t.stride(1) != 1:
+        raise ValueError(f"{name}: rows must be contiguous")
+    ld = t.stride(0) if B > 1 else N
+    if ld < N:
+        raise ValueError(f"{name}: row stride {ld} < N = {N}")
+    return ld
+
+
+def _vecN(t: torch.Tensor | None, name: str, n: int):
+    if t is not None:
+        _f32(t, name)
+        if t.numel() != n:
+            raise ValueError(f"{name}: must hold {n} elements, got {tuple(t.shape)}")
+    return t
+
+
+def bn_forward(x: torch.Tensor, gamma, beta, running_mean, running_var, *, eps: float = 1e-5,
+               momentum: float = 0.1, training: bool = True, relu: bool = False,
+               out: torch.Tensor | None = None, save: bool = True) -> dict:
+    """nn.BatchNorm1d (+ReLU) on x [B, N]: dict(y, mean, mean_lo, invstd, invstd_lo).
+    Training mode normalises with the batch statistics (fp64 two-pass), updates the running
+    statistics in place and, with save, returns what bn_backward needs (the *_lo vectors are
+    the parts of the fp64 statistics that fp32 drops); eval mode reads the running ones.
+    out: where y goes, e.g. the first N columns of a wider matrix."""
+    ldx = _ld2(x, "x")
+    B, N = x.shape
+    if out is None:
+        out = torch.empty(B, N, dtype=torch.float32, device=x.device)
+    ldy = _ld2(out, "out")
+    if tuple(out.shape) != (B, N):
+        raise ValueError(f"bn_forward: out must be [{B}, {N}]")
+    for t, nm in ((gamma, "gamma"), (beta, "beta"), (running_mean, "running_mean"),
+                  (running_var, "running_var")):
+        _vecN(t, nm, N)
+    mean = lo = inv = inv_lo = None
+    if training and save:
+        stats = torch.empty(4, N, dtype=torch.float32, device=x.device)
+        mean, lo, inv, inv_lo = stats[0], stats[1], stats[2], stats[3]
+    lib.ctr_bn_forward(B, N, _p(x), ldx, _p(gamma), _p(beta), _p(running_mean), _p(running_var),
+                       float(eps), float(momentum), int(training), int(relu), _p(out), ldy,
+                       _p(mean), _p(lo), _p(inv), _p(inv_lo), _stream())
+    return dict(y=out, mean=mean, mean_lo=lo, invstd=inv, invstd_lo=inv_lo)
+
+
+def bn_backward(dy: torch.Tensor, x: torch.Tensor, mean, invstd, gamma, *, y=None,
+                relu: bool = False, mean_lo=None, invstd_lo=None, want_dx: bool = True,
+                dx: torch.Tensor | None = None) -> dict:
+    """Training-mode BatchNorm1d (+ReLU) backward in one launch: dict(dgamma, dbeta, dx)."""
+    lddy = _ld2(dy, "dy")
+    B, N = dy.shape
+    ldx = _ld2(x, "x")
+    if tuple(x.shape) != (B, N):
+        raise ValueError(f"bn_backward: x must be [{B}, {N}]")
+    ldy = 0
+    if relu:
+        if y is None or tuple(y.shape) != (B, N):
+            raise ValueError(f"bn_backward: relu needs the forward's y [{B}, {N}]")
+        ldy = _ld2(y, "y")
+    for t, nm in ((mean, "mean"), (invstd, "invstd"), (gamma, "gamma"), (mean_lo, "mean_lo"),
+                  (invstd_lo, "invstd_lo")):
+        _vecN(t, nm, N)
+    out = torch.empty(2, N, dtype=torch.float32, device=dy.device)
+    ldd = 0
+    if want_dx:
+        if dx is None:
+            dx = torch.empty(B, N, dtype=torch.float32, device=dy.device)
+        ldd = _ld2(dx, "dx")
+        if tuple(dx.shape) != (B, N):
+            raise ValueError(f"bn_backward: dx must be [{B}, {N}]")
+    else:
+        dx = None
+    lib.ctr_bn_backward(B, N, _p(dy), lddy, _p(y) if relu else None, ldy, int(relu), _p(x), ldx,
+                        _p(mean), _p(mean_lo), _p(invstd), _p(invstd_lo), _p(gamma), _p(out[0]),
+                        _p(out[1]), _p(dx), ldd, _stream())
+    return dict(dgamma=out[0], dbeta=out[1], dx=dx)
+
+
+def td3_noise(n: int, seed: int, offset: int = 0, out: torch.Tensor | None = None,
+              device=None) -> torch.Tensor:
+    """n unit-normal draws, elements offset .. offset + n - 1 of stream `seed`: bitwise what
+    td3_act / td3_smooth consume in seed mode (head h of a [B, A] pair starts at h * B * A)."""
+    if out is None:
+        out = torch.empty(n, dtype=torch.float32, device=device if device is not None else "cuda")
+    _f32(out, "out")
+    if out.numel() < n:
+        raise ValueError("td3_noise: out is shorter than n")
+    lib.ctr_td3_noise(n, int(seed) & (2**64 - 1), int(offset) & (2**64 - 1), _p(out), _stream())
+    return out
+
+
+def _td3_noise_args(noise, seed, B: int, A: int):
+    if noise is not None:
+        n_c, n_d = noise
+        for t, nm in ((n_c, "noise_c"), (n_d, "noise_d")):
+            _f32(t, nm)
+            if tuple(t.shape) != (B, A):
+                raise ValueError(f"{nm}: must be [{B}, {A}]")
+        return TD3_NOISE_PTR, n_c, n_d, 0
+    if seed is not None:
+        return TD3_NOISE_SEED, None, None, int(seed) & (2**64 - 1)
+    return TD3_NOISE_NONE, None, None, 0
+
+
+def td3_act(pre_c: torch.Tensor, pre_d: torch.Tensor, *, noise=None, seed=None,
+            sigma: float = 0.1, want_softmax: bool = True, want_index: bool = True) -> dict:
+    """The action heads from their pre-activations [B, A]: tanh, then (noise=(n_c, n_d) or
+    seed=) clamp(v + sigma * noise, -1, 1): dict(c_actions, c_softmax, d_actions, d_index
+    [B, 1] int64 = argmax + 1, the lowest index among equal values)."""
+    ldp = _ld2(pre_c, "pre_c")
+    B, A = pre_c.shape
+    if tuple(pre_d.shape) != (B, A) or _ld2(pre_d, "pre_d") != ldp:
+        raise ValueError("td3_act: pre_c and pre_d must have one shape and row stride")
+    mode, n_c, n_d, sd = _td3_noise_args(noise, seed, B, A)
+    dev = pre_c.device
+    c = torch.empty(B, A, dtype=torch.float32, device=dev)
+    d = torch.empty(B, A, dtype=torch.float32, device=dev)
+    sm = torch.empty(B, A, dtype=torch.float32, device=dev) if want_softmax else None
+    ix = torch.empty(B, 1, dtype=torch.int64, device=dev) if want_index else None
+    lib.ctr_td3_act(B, A, _p(pre_c), _p(pre_d), ldp, mode, _p(n_c), _p(n_d), sd, float(sigma),
+                    _p(c), _p(sm), _p(d), _p(ix), _stream())
+    return dict(c_actions=c, c_softmax=sm, d_actions=d, d_index=ix)
+
+
+def td3_smooth(mean_c: torch.Tensor, mean_d: torch.Tensor, out_c: torch.Tensor,
+               out_d: torch.Tensor, *, noise=None, seed=None, apply_tanh: bool = False) -> None:
+    """Target policy smoothing of both heads, clamp(mean + clamp(0.2 * noise, -0.5, 0.5), -1, 1),
+    written to out_c / out_d: two [B, A] column blocks of one matrix (the target critic's
+    input). apply_tanh: the means are pre-activations."""
+    ldm = _ld2(mean_c, "mean_c")
+    B, A = mean_c.shape
+    if tuple(mean_d.shape) != (B, A) or _ld2(mean_d, "mean_d") != ldm:
+        raise ValueError("td3_smooth: mean_c and mean_d must have one shape and row stride")
+    ldo = _ld2(out_c, "out_c")
+    if tuple(out_c.shape) != (B, A) or tuple(out_d.shape) != (B, A) or _ld2(out_d, "out_d") != ldo:
+        raise ValueError(f"td3_smooth: out_c and out_d must be [{B}, {A}] with one row stride")
+    mode, n_c, n_d, sd = _td3_noise_args(noise, seed, B, A)
+    lib.ctr_td3_smooth(B, A, _p(mean_c), _p(mean_d), ldm, int(apply_tanh), mode, _p(n_c), _p(n_d),
+                       sd, _p(out_c), _p(out_d), ldo, _stream())
+
+
+def td3_critic_loss(q1, q2, q1_t, q2_t, r: torch.Tensor, isw, gamma: float) -> dict:
+    """The twin critics' importance-weighted loss and everything derived from it in one launch:
+    dict(q_target, td, dq1, dq2 [B, 1], loss (0-dim)). r: [B] or [B, 1], any stride."""
+    B = q1.numel()
+    for t, nm in ((q1, "q1"), (q2, "q2"), (q1_t, "q1_t"), (q2_t, "q2_t"), (isw, "isw")):
+        _vecN(t, nm, B)
+    _dev(r, "r")
+    if r.dtype != torch.float32 or r.numel() != B or r.dim() not in (1, 2) or \
+            (r.dim() == 2 and r.shape[1] != 1):
+        raise ValueError(f"td3_critic_loss: r must be float32 [{B}] or [{B}, 1]")
+    ldr = r.stride(0) if B > 1 else 1
+    if ldr < 1:
+        raise ValueError("td3_critic_loss: r must have a positive stride")
+    o = torch.empty(4, B, 1, dtype=torch.float32, device=q1.device)
+    loss = torch.empty(1, dtype=torch.float32, device=q1.device)
+    lib.ctr_td3_critic_loss(B, _p(q1), _p(q2), _p(q1_t), _p(q2_t), _p(r), ldr, _p(isw),
+                            float(gamma), _p(o[0]), _p(o[1]), _p(loss), _p(o[2]), _p(o[3]),
+                            _stream())
+    return dict(q_target=o[0], td=o[1], dq1=o[2], dq2=o[3], loss=loss.reshape(()))
+
+
+class SoftUpdateTable:
+    """The device table of (target, source, numel) triples of ctr_soft_update_multi, built
+    once for a list of tensor pairs and kept (it holds the tensors, so their addresses stay
+    valid). matches() tells whether it still describes a given list of pairs."""
+
+    def __init__(self, targets, sources):
+        targets, sources = list(targets), list(sources)
+        if len(targets) != len(sources) or not targets:
+            raise ValueError("SoftUpdateTable: one source per target, at least one")
+        rows = []
+        for t, s in zip(targets, sources):
+            _f32(t, "target")
+            _f32(s, "source")
+            if t.shape != s.shape or t.device != s.device:
+                raise ValueError("SoftUpdateTable: a target and its source differ in shape/device")
+            if t.numel():
+                rows.append((t.data_ptr(), s.data_ptr(), t.numel()))
+        self.tensors = (targets, sources)
+        self.key = tuple(rows)
+        self.count = len(rows)
+        self.max_numel = max((r[2] for r in rows), default=0)
+        self.device = targets[0].device
+        self.table = torch.tensor(rows, dtype=torch.int64).to(self.device) if rows else None
+
+    def matches(self, targets, sources) -> bool:
+        return self.key == tuple((t.data_ptr(), s.data_ptr(), t.numel())
+                                 for t, s in zip(targets, sources) if t.numel())
+
+
+def soft_update_multi(table: SoftUpdateTable, tau: float) -> None:
+    """target = target * (1 - tau) + source * tau over every pair of the table, one launch."""
+    if table.count == 0:
+        return
+    lib.ctr_soft_update_multi(table.count, _p(table.table), table.max_numel, float(tau),
+                              _stream())
 
 
 def ensemble_preds(preds: torch.Tensor, actions: torch.Tensor, prob_weights: torch.Tensor,
