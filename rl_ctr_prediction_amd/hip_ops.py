@@ -36,12 +36,18 @@ __all__ = [
 
 
 # ----------------------------------------------------------------------- plumbing ----
+class HostTensorError(RuntimeError, TypeError):
+    """A host tensor where a kernel needs a device one: the RuntimeError every wrapper has
+    always raised for it, and a TypeError (an argument of the wrong kind, refused before any
+    launch) for callers that catch argument errors as TypeError / ValueError."""
+
+
 def _dev(t: torch.Tensor, name: str = "tensor") -> torch.Tensor:
     if not isinstance(t, torch.Tensor):
         raise TypeError(f"{name}: expected a torch.Tensor")
     if t.device.type != "cuda":
-        raise RuntimeError(f"{name} is on {t.device}: the HIP hot path needs ROCm device "
-                           "tensors (there is no CPU fallback)")
+        raise HostTensorError(f"{name} is on {t.device}: the HIP hot path needs ROCm device "
+                              "tensors (there is no CPU fallback)")
     return t
 
 
@@ -513,6 +519,7 @@ class SparsePlanBuffers:
         self.seg_offsets = torch.empty(c + 1, **i32)
         self.num_unique = torch.zeros(1, **i32)
         self.S = 0
+        self._n_unique = None  # num_unique as the host last read it for the current build
         self._struct = SparsePlan()
         # the plan's own radix scratch (not the per-stream Workspace): plans are built on the
         # plan streams concurrently with steps, and their captured graphs replay there, so
@@ -539,6 +546,7 @@ class SparsePlanBuffers:
         if S > self.capacity:
             raise ValueError(f"sparse plan: {S} slots > capacity {self.capacity}")
         self.S = S
+        self._n_unique = None
         need = lib.ctr_sparse_plan_workspace_bytes(S, int(V))
         if need < 0:
             raise RuntimeError(lib.load().ctr_last_error().decode())
@@ -571,6 +579,7 @@ class SparsePlanBuffers:
         if mask.dtype != torch.int32 or mask.numel() < (n_rows + 3) // 4:
             raise ValueError("build_runs: mask must be int32[ceil(n_rows / 4)]")
         self.S = S
+        self._n_unique = None
         need = lib.ctr_sparse_plan_runs_workspace_bytes(int(n_runs), S // n_runs, int(n_rows))
         if need < 0:
             raise RuntimeError(lib.load().ctr_last_error().decode())
@@ -584,7 +593,15 @@ class SparsePlanBuffers:
         return self
 
     def num_unique_host(self) -> int:
-        return int(self.num_unique.item())
+        self._n_unique = int(self.num_unique.item())
+        return self._n_unique
+
+    def max_unique(self, V: int) -> int:
+        """How many unique rows the plan can have, as far as the host knows without a sync:
+        the count it last read for this build (num_unique_host), else min(S, V). (A plan
+        rebuilt by a graph replay keeps the count read before; whoever sizes a buffer by the
+        new count has read it, which refreshes this one.)"""
+        return min(self.S, int(V)) if self._n_unique is None else self._n_unique
 
     def slot_to_unique(self, out: torch.Tensor | None = None) -> torch.Tensor:
         """int32[S]: the unique-row ordinal of every slot."""
@@ -801,10 +818,58 @@ def segment_sum_rows(plan: SparsePlanBuffers, vals, vals_lin=None, rowmap=None, 
     return out, out_lin
 
 
+def _i32(t, name: str, n: int) -> torch.Tensor:
+    """A contiguous int32 device tensor of n elements (last / rowmap / owner / step counters):
+    the kernels index it without a bound of their own."""
+    _dev(t, name)
+    if t.dtype != torch.int32:
+        raise TypeError(f"{name}: expected int32, got {t.dtype}")
+    if t.numel() != n or not t.is_contiguous():
+        raise ValueError(f"{name}: expected {n} contiguous int32 elements, got shape "
+                         f"{tuple(t.shape)}")
+    return t
+
+
+def _adam_tables(emb, m_emb, v_emb, lin, m_lin, v_lin) -> tuple[int, int]:
+    """The (parameter, exp_avg, exp_avg_sq) tables of an Adam kernel: contiguous float32
+    device matrices, the moments of the parameter's shape; the linear table's three (V
+    elements each, [V] or [V, 1]) all given or all None. Returns (V, K)."""
+    _f32(emb, "emb")
+    if emb.dim() != 2:
+        raise ValueError(f"emb: expected a [V, K] table, got shape {tuple(emb.shape)}")
+    for t, n in ((m_emb, "m_emb"), (v_emb, "v_emb")):
+        if _f32(t, n).shape != emb.shape:
+            raise ValueError(f"{n}: shape {tuple(t.shape)} != emb's {tuple(emb.shape)}")
+    V, K = emb.shape
+    if lin is None:
+        if m_lin is not None or v_lin is not None:
+            raise ValueError("lin, m_lin and v_lin must be all given or all None")
+    else:
+        for t, n in ((lin, "lin"), (m_lin, "m_lin"), (v_lin, "v_lin")):
+            if _f32(t, n).numel() != V:
+                raise ValueError(f"{n}: expected {V} elements, got shape {tuple(t.shape)}")
+    return V, K
+
+
+def _plan_grads(plan: "SparsePlanBuffers", V: int, K: int, grad_rows, grad_lin, lin,
+                names=("grad_rows", "grad_lin")) -> None:
+    """The per-row gradient buffers of a plan: float32, at least as many rows as the plan
+    can have unique rows (SparsePlanBuffers.max_unique: num_unique lives on the device)."""
+    n = plan.max_unique(V)
+    if _f32(grad_rows, names[0]).numel() < n * K:
+        raise ValueError(f"{names[0]}: {tuple(grad_rows.shape)} holds fewer than the plan's "
+                         f"possible {n} rows of {K}")
+    if grad_lin is not None:
+        if _f32(grad_lin, names[1]).numel() < n:
+            raise ValueError(f"{names[1]}: fewer than the plan's possible {n} rows")
+    elif lin is not None:
+        raise ValueError(f"{names[1]} is needed with a linear table")
+
+
 def _deferred_table(emb, m_emb, v_emb, lin, m_lin, v_lin, last):
     from ._lib import DeferredTable
-    for t, n in ((emb, "emb"), (m_emb, "m_emb"), (v_emb, "v_emb")):
-        _f32(t, n)
+    V, _ = _adam_tables(emb, m_emb, v_emb, lin, m_lin, v_lin)
+    _i32(last, "last", V)
     return DeferredTable(_p(emb), _p(m_emb), _p(v_emb), _p(lin), _p(m_lin), _p(v_lin), _p(last))
 
 
@@ -835,11 +900,24 @@ def fm_embedding_grad_adam(plan: SparsePlanBuffers, F: int, gz, sum_e, dx, table
     """fm_embedding_grad + adam_deferred_rows(sums, step = *step_dev) with the apply fused
     into the combine pass (ctr_fm_embedding_grad_adam): table = (E, m_E, v_E, w, m_w, v_w,
     last); grad_rows / grad_lin are scratch, holding every row's sum with keep_sums."""
-    K = table[0].shape[1]
+    dtab = _deferred_table(*table)
+    V, K = table[0].shape
+    _i32(step_dev, "step_dev", 1)
+    if int(F) < 1:
+        raise ValueError("fm_embedding_grad_adam: F must be >= 1")
+    B = -(-plan.S // int(F))  # slot s belongs to example s // F
+    if _f32(gz, "gz").numel() < B or _f32(sum_e, "sum_e").numel() < B * K:
+        raise ValueError(f"fm_embedding_grad_adam: gz [B] and sum_e [B, {K}] must cover the "
+                         f"plan's {plan.S} = B * F slots")
+    if dx is not None and _f32(dx, "dx").numel() < plan.S * K:
+        raise ValueError(f"fm_embedding_grad_adam: dx must be [{plan.S}, {K}]")
+    if grad_lin is None:
+        raise ValueError("fm_embedding_grad_adam: grad_rows and grad_lin are needed")
+    _plan_grads(plan, V, K, grad_rows, grad_lin, table[3])
     ws = _seg_ws(plan, K)
     tab = step_table.ensure(step)
     lib.ctr_fm_embedding_grad_adam(plan.struct(), int(F), int(K), _p(gz), _p(sum_e), _p(dx),
-                                   _deferred_table(*table), _p(step_dev), _p(tab),
+                                   dtab, _p(step_dev), _p(tab),
                                    float(betas[0]), float(betas[1]), float(eps),
                                    float(weight_decay), _p(grad_rows), _p(grad_lin),
                                    int(keep_sums), _p(ws), ws.numel(), _stream())
@@ -849,11 +927,22 @@ def segment_sum_rows_adam(plan: SparsePlanBuffers, vals, vals_lin, table, step_d
                           step_table: "AdamStepTable", step: int, betas=(0.9, 0.999), eps=1e-8,
                           weight_decay=0.0, out=None, out_lin=None, keep_sums: bool = False) -> None:
     """segment_sum_rows + adam_deferred_rows in one pass (ctr_segment_sum_rows_adam)."""
-    K = vals.shape[1]
+    dtab = _deferred_table(*table)
+    V, K = table[0].shape
+    _i32(step_dev, "step_dev", 1)
+    if _f32(vals, "vals").dim() != 2 or vals.shape[1] != K or vals.shape[0] < plan.S:
+        raise ValueError(f"segment_sum_rows_adam: vals must be [>= {plan.S}, {K}], got "
+                         f"{tuple(vals.shape)}")
+    if vals_lin is not None and _f32(vals_lin, "vals_lin").numel() < plan.S:
+        raise ValueError(f"segment_sum_rows_adam: vals_lin needs {plan.S} elements")
+    if out is None or (vals_lin is None) != (out_lin is None):
+        raise ValueError("segment_sum_rows_adam: out is needed, and out_lin exactly when "
+                         "vals_lin is given")
+    _plan_grads(plan, V, K, out, out_lin, None, names=("out", "out_lin"))
     ws = _seg_ws(plan, K)
     tab = step_table.ensure(step)
     lib.ctr_segment_sum_rows_adam(plan.struct(), int(K), _p(vals), _p(vals_lin),
-                                  _deferred_table(*table), _p(step_dev), _p(tab),
+                                  dtab, _p(step_dev), _p(tab),
                                   float(betas[0]), float(betas[1]), float(eps),
                                   float(weight_decay), _p(out), _p(out_lin), int(keep_sums),
                                   _p(ws), ws.numel(), _stream())
@@ -879,13 +968,26 @@ def adam_scalars(step: int, lr: float, betas=(0.9, 0.999)) -> tuple[float, float
     return lr / bias_correction1, bias_correction2 ** 0.5
 
 
+def _step_dev_ok(name: str, step_dev, table) -> None:
+    """step_dev (optional): one int32 on the device, read by the kernel; it indexes the step
+    table, so the table must be given with it."""
+    if step_dev is None:
+        return
+    _i32(step_dev, "step_dev", 1)
+    if table is None:
+        raise ValueError(f"{name}: step_dev needs the step table")
+
+
 def adam_dense(p, g, m, v, step: int, lr: float, betas=(0.9, 0.999), eps=1e-8,
                weight_decay=0.0, step_dev=None, table=None, planes=None) -> None:
     """One Adam step; with step_dev/table the step index is read on the device (graphs).
     planes: [(offset, Planes)] — sub-matrices p[offset : offset + rows*cols] (row-major,
     the Planes' shape) whose planes are rewritten with the updated values (ctr_adam_dense_planes)."""
     for t, n in ((p, "param"), (g, "grad"), (m, "exp_avg"), (v, "exp_avg_sq")):
-        _f32(t, n)
+        if _f32(t, n).numel() != p.numel():
+            raise ValueError(f"adam_dense: {n} has shape {tuple(t.shape)}, param "
+                             f"{tuple(p.shape)}")
+    _step_dev_ok("adam_dense", step_dev, table)
     ss, bc2s = adam_scalars(max(step, 1), lr, betas)
     tab = table.ensure(step) if table is not None else None
     args = (_p(p), _p(g), _p(m), _p(v), p.numel(), ss, bc2s, _p(tab), _p(step_dev),
@@ -901,7 +1003,14 @@ def adam_dense(p, g, m, v, step: int, lr: float, betas=(0.9, 0.999), eps=1e-8,
 def adam_embedding(emb, m_emb, v_emb, lin, m_lin, v_lin, rowmap, grad_rows, grad_lin, step: int,
                    lr: float, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0, step_dev=None,
                    table=None) -> None:
-    V, K = emb.shape
+    V, K = _adam_tables(emb, m_emb, v_emb, lin, m_lin, v_lin)
+    _i32(rowmap, "rowmap", V)
+    # rowmap's entries (device values) index grad_rows / grad_lin: only their kind is known here
+    if _f32(grad_rows, "grad_rows").numel() % K:
+        raise ValueError(f"adam_embedding: grad_rows must hold rows of {K}")
+    if lin is not None:
+        _f32(grad_lin, "grad_lin")
+    _step_dev_ok("adam_embedding", step_dev, table)
     ss, bc2s = adam_scalars(max(step, 1), lr, betas)
     tab = table.ensure(step) if table is not None else None
     lib.ctr_adam_embedding(_p(emb), _p(m_emb), _p(v_emb), _p(lin), _p(m_lin), _p(v_lin), V, K,
@@ -954,7 +1063,12 @@ def adam_deferred_rows(emb, m_emb, v_emb, lin, m_lin, v_lin, last, plan: "Sparse
     """grad_rows None: bring the plan's rows to `step`; else to step-1 and apply `step`.
     step_dev (device int32): read the step there instead (graphs); `step` then only sizes
     the table."""
-    V, K = emb.shape
+    V, K = _adam_tables(emb, m_emb, v_emb, lin, m_lin, v_lin)
+    _i32(last, "last", V)
+    if grad_rows is not None:
+        _plan_grads(plan, V, K, grad_rows, grad_lin, lin)
+    if step_dev is not None:
+        _i32(step_dev, "step_dev", 1)
     tab = table.ensure(max(step, 1))
     lib.ctr_adam_deferred_rows(_p(emb), _p(m_emb), _p(v_emb), _p(lin), _p(m_lin), _p(v_lin), V, K,
                                _p(last), plan.struct(), _p(grad_rows), _p(grad_lin),
@@ -971,9 +1085,12 @@ def adam_deferred_entries(emb, m_emb, v_emb, lin, m_lin, v_lin, last, plan: "Spa
     unique row of `plan` (over the received entries) stepped with the sequential sum of its
     entries' vals / vals_lin; skip_row left alone. run_len > 0: vals is the chunked exchange
     buffer (shard_rows_pack's layout, rows_chunk(run_len, K, lin) floats per chunk)."""
-    V, K = emb.shape
+    V, K = _adam_tables(emb, m_emb, v_emb, lin, m_lin, v_lin)
+    _i32(last, "last", V)
+    if step_dev is not None:
+        _i32(step_dev, "step_dev", 1)
     _f32(vals, "vals")
-    chunk = rows_chunk(run_len, K, lin is not None) if run_len else 0
+    chunk =rows_chunk(run_len, K, lin is not None) if run_len else 0
     if run_len == 0 and (vals.dim() != 2 or vals.shape[1] != K):
         raise ValueError(f"adam_deferred_entries: vals must be [entries, {K}]")
     tab = table.ensure(max(step, 1))
@@ -992,7 +1109,10 @@ def adam_deferred_catchup_ids(emb, m_emb, v_emb, lin, m_lin, v_lin, last, idx: t
     """Bring the rows of a batch's ids to the completed step held in step_dev (device int32),
     no sparse plan needed; owner is an int32[V] scratch. step_hint (>= the device value)
     sizes the step table."""
-    V, K = emb.shape
+    V, K = _adam_tables(emb, m_emb, v_emb, lin, m_lin, v_lin)
+    _i32(last, "last", V)
+    _i32(owner, "owner", V)
+    _i32(step_dev, "step_dev", 1)
     idx, it = _idx(idx)
     tab = table.ensure(max(step_hint, 1))
     lib.ctr_adam_deferred_catchup_ids(_p(emb), _p(m_emb), _p(v_emb), _p(lin), _p(m_lin), _p(v_lin),
@@ -1037,6 +1157,9 @@ def fm_step_tail(loss_elem: torch.Tensor, gz: torch.Tensor, loss_scale: float,
         raise ValueError("fm_step_tail: loss_elem / gz of B elements, one bias gradient")
     if not (g.numel() == m.numel() == v.numel() == p.numel()):
         raise ValueError("fm_step_tail: p, g, m, v of one size")
+    for t, n in ((loss_out, "loss_out"), (bias_grad, "bias_grad")):
+        _f32(t, n)
+    _i32(step_ctr, "step_ctr", 2)
     tab = table.ensure(step)
     lib.ctr_fm_step_tail(_p(loss_elem), _p(gz), B, float(loss_scale), _p(loss_out),
                          _p(bias_grad), _p(p), _p(g), _p(m), _p(v), p.numel(), _p(tab),
@@ -1048,7 +1171,8 @@ def fm_step_tail(loss_elem: torch.Tensor, gz: torch.Tensor, loss_scale: float,
 def adam_deferred_flush(emb, m_emb, v_emb, lin, m_lin, v_lin, last, step: int,
                         table: AdamStepTable, betas=(0.9, 0.999), eps=1e-8,
                         weight_decay=0.0) -> None:
-    V, K = emb.shape
+    V, K = _adam_tables(emb, m_emb, v_emb, lin, m_lin, v_lin)
+    _i32(last, "last", V)
     tab = table.ensure(step)
     lib.ctr_adam_deferred_flush(_p(emb), _p(m_emb), _p(v_emb), _p(lin), _p(m_lin), _p(v_lin), V, K,
                                 _p(last), int(step), _p(tab), float(betas[0]), float(betas[1]),
