@@ -706,6 +706,54 @@ int ctr_per_sample(int64_t N, int T, int64_t n_valid, int k, int mode, uint64_t 
                    float* batch, float* isw, float* min_p, void* ws, int64_t ws_bytes,
                    ctr_stream_t stream);
 
+/* ---------------------------------- Evaluation metrics: exact ROC AUC, BCE loss, rewards --
+ * What the drivers' test() computes on the host (sklearn's roc_auc_score over .tolist()ed
+ * predictions, a .item() per batch loss, torch.sum(rewards).item()), kept on the device with
+ * no host read: batches are appended to a record buffer, and one call sorts and reduces it.
+ * records [cap] (8-byte words), the workspace (ctr_metrics_workspace_bytes(cap), 16-byte
+ * aligned) and the state block (CTR_METRICS_STATE_BYTES, 8-byte aligned) are caller-owned
+ * device memory; 1 <= cap < 2^31. The state block is sixteen 8-byte words:
+ *   [0] U2, [1] P, [2] N (uint64)     written by ctr_metrics_auc
+ *   [3] loss_sum (fp64)               sum over loss batches of (batch BCE sum / batch size)
+ *   [4] nll_sum (fp64)                sum of every example's BCE
+ *   [5] reward_sum (fp64)
+ *   [6] batches, [7] loss_count (int64)   appends with the loss, and their examples
+ *   [8] low 32 bits: CTR_METRICS_FLAG_* bits (int32); the rest is reserved (zero)
+ * ctr_metrics_reset zeroes it (one memset on the stream).
+ * ctr_metrics_append: example i < n (prediction pred[i * stride], stride >= 1 in elements;
+ *   label labels[i], contiguous, of type CTR_LABEL_*; reward rewards[i], optional) becomes
+ *   records[offset + i] = (key << 1) | label, key the order-preserving uint32 image of the
+ *   fp32 bits of pred + 0.0f (so -0.0 and +0.0 tie, as they do in sklearn). The host passes the
+ *   offset: there is no device counter. With with_loss != 0 the batch's BCE
+ *   -(y max(log p, -100) + (1 - y) max(log(1 - p), -100)) (log in double of the fp32 p) is
+ *   summed in fp64 and words [3], [4], [6], [7] advance; rewards advance word [5]. One launch
+ *   for n <= 16384, two above; every sum in an order fixed by n, no floating-point atomics: the
+ *   same inputs give the same bits. A NaN prediction, a label other than 0/1, and with the loss
+ *   a prediction outside [0, 1] OR their flag into word [8] and add nothing to the loss; nothing
+ *   faults and nothing outside records[offset, offset + n) is written. n == 0: no launch.
+ * ctr_metrics_auc: sorts records[0, count) by their low 33 bits in place (stable LSD radix
+ *   sort, two launches per pass, the workspace holds the second buffer) and writes
+ *   P = positives, N = negatives, U2 = sum over positives of (2 * negatives with a smaller
+ *   prediction + negatives with an equal one), all exact integers:
+ *   AUC = U2 / (2 P N), one division left to the host. count == 0: no launch.
+ * ctr_metrics_tile: records per sort / reduce tile (the sizes around which tests probe). */
+#define CTR_METRICS_STATE_BYTES 128
+enum ctr_label_type { CTR_LABEL_F32 = 0, CTR_LABEL_I32 = 1, CTR_LABEL_I64 = 2 };
+enum ctr_metrics_flag {
+  CTR_METRICS_FLAG_NAN = 1,    /* a NaN prediction */
+  CTR_METRICS_FLAG_LABEL = 2,  /* a label other than 0 / 1 */
+  CTR_METRICS_FLAG_RANGE = 4   /* a prediction outside [0, 1] while the loss was asked for */
+};
+int ctr_metrics_tile(void);
+int64_t ctr_metrics_workspace_bytes(int64_t cap);
+int ctr_metrics_reset(void* state, ctr_stream_t stream);
+int ctr_metrics_append(int64_t cap, int64_t offset, int64_t n, const float* pred,
+                       int64_t stride, const void* labels, int label_type,
+                       const float* rewards, int with_loss, uint64_t* records, void* ws,
+                       int64_t ws_bytes, void* state, ctr_stream_t stream);
+int ctr_metrics_auc(int64_t cap, int64_t count, uint64_t* records, void* ws, int64_t ws_bytes,
+                    void* state, ctr_stream_t stream);
+
 /* ------------------------------------------- Hybrid TD3 agent (actor, twin critics) -----
  * The small kernels of Critic, hybrid_actors and Hybrid_TD3_Model.learn
  * (Hybrid_TD3_model_PER.py:111-393); the Linear layers run on ctr_gemm_f32_ex. All fp32, no

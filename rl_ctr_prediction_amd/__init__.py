@@ -9,6 +9,7 @@ running on hand-written gfx950 HIP kernels behind the C ABI in include/ctr_hip.h
 from .feature_embedding import Feature_Embedding
 from .ffm_trainer import FusedFFMTrainer
 from .hybrid_td3_model_per import Critic, Hybrid_TD3_Model, hybrid_actors
+from .metrics import DeviceMetrics, roc_auc_score
 from .optim import DenseAdam
 from .p_model import DCN, FFM, FM, FNN, DeepFM, InnerPNN
 from .pg_model import Net, PolicyGradient
@@ -18,4 +19,4 @@ from .trainer import FusedCTRTrainer
 
 __all__ = ["FM", "FFM", "DeepFM", "InnerPNN", "FNN", "DCN", "Feature_Embedding", "Net", "PolicyGradient", "FusedCTRTrainer",
            "FusedFFMTrainer", "ShardedCTRTrainer", "DenseAdam", "PrioritizedMemory",
-           "Hybrid_TD3_Model", "Critic", "hybrid_actors"]
+           "Hybrid_TD3_Model", "Critic", "hybrid_actors", "DeviceMetrics", "roc_auc_score"]

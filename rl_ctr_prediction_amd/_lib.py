@@ -16,6 +16,9 @@ CTR_OK = 0
 CTR_IDX_I32, CTR_IDX_I64 = 0, 1
 CTR_EFLAG_INDEX = 1
 CTR_EFLAG_CAPACITY = 2
+CTR_LABEL_F32, CTR_LABEL_I32, CTR_LABEL_I64 = 0, 1, 2
+CTR_METRICS_FLAG_NAN, CTR_METRICS_FLAG_LABEL, CTR_METRICS_FLAG_RANGE = 1, 2, 4
+CTR_METRICS_STATE_BYTES = 128
 EPI_NONE, EPI_BIAS, EPI_BIAS_RELU, EPI_BIAS_RELU_DROP, EPI_GRAD_MASK = range(5)
 
 _vp, _i32, _i64, _f32, _f64, _u64 = C.c_void_p, C.c_int, C.c_int64, C.c_float, C.c_double, C.c_uint64
@@ -287,6 +290,12 @@ SIGNATURES = {
     "ctr_per_keys": (_i32, [_i64, _vp, _i32, _u64, _vp, _vp]),
     "ctr_per_sample": (_i32, [_i64, _i32, _i64, _i32, _i32, _u64, _f32, _vp, _vp, _vp, _vp, _vp,
                               _vp, _vp, _i64, _vp]),
+    "ctr_metrics_tile": (_i32, []),
+    "ctr_metrics_workspace_bytes": (_i64, [_i64]),
+    "ctr_metrics_reset": (_i32, [_vp, _vp]),
+    "ctr_metrics_append": (_i32, [_i64, _i64, _i64, _vp, _i64, _vp, _i32, _vp, _i32, _vp, _vp,
+                                  _i64, _vp, _vp]),
+    "ctr_metrics_auc": (_i32, [_i64, _i64, _vp, _vp, _i64, _vp, _vp]),
     "ctr_bn_forward": (_i32, [_i64, _i32, _vp, _i64, _vp, _vp, _vp, _vp, _f32, _f32, _i32, _i32,
                               _vp, _i64, _vp, _vp, _vp, _vp, _vp]),
     "ctr_bn_backward": (_i32, [_i64, _i32, _vp, _i64, _vp, _i64, _i32, _vp, _i64, _vp, _vp, _vp,
@@ -342,7 +351,7 @@ class _Lib:
             raise AttributeError(name)
         fn = self.raw(name)
         res = SIGNATURES[name][0]
-        if res is not _i32 or name in ("ctr_abi_version", "ctr_device_count"):
+        if res is not _i32 or name in ("ctr_abi_version", "ctr_device_count", "ctr_metrics_tile"):
             self.__dict__[name] = fn
             return fn
 

@@ -23,7 +23,7 @@ ARCH = os.environ.get("CTR_OFFLOAD_ARCH", "gfx950")
 
 SOURCES = ["abi.cpp", "fm_forward.hip", "sparse_plan.hip", "sparse_grad.hip", "adam.hip",
            "gemm.hip", "gemm_sb16.hip", "gemm_planes.hip", "reduce_pg.hip", "pnn.hip", "dcn.hip", "per.hip", "td3.hip", "io.cpp", "ensemble.hip", "ffm.hip",
-           "layout.hip", "ops.hip"]
+           "layout.hip", "ops.hip", "metrics.hip"]
 INCLUDE_DIRS = [CSRC, ROOT / "include"]
 
 CXXFLAGS = ["-O3", "-std=c++17", "-fPIC", f"--offload-arch={ARCH}",

@@ -14,7 +14,8 @@ from dataclasses import dataclass
 
 import torch
 
-from ._lib import (CTR_EFLAG_CAPACITY, CTR_EFLAG_INDEX, CTR_IDX_I32, CTR_IDX_I64, EPI_BIAS, EPI_BIAS_RELU,
+from ._lib import (CTR_EFLAG_CAPACITY, CTR_EFLAG_INDEX, CTR_IDX_I32, CTR_IDX_I64, CTR_LABEL_F32,
+                   CTR_LABEL_I32, CTR_LABEL_I64, EPI_BIAS, EPI_BIAS_RELU,
                    EPI_BIAS_RELU_DROP, EPI_GRAD_MASK, EPI_NONE, PlanesDesc, PlaneViewDesc, SparsePlan,
                    CtrHipError, lib)
 
@@ -25,6 +26,8 @@ __all__ = [
     "rows_to_dense", "adam_dense", "fm_step_tail", "adam_embedding", "adam_scalars", "feature_embedding",
     "dcn_cross_forward", "dcn_cross_backward",
     "per_add", "per_update", "per_keys", "per_sample", "PER_STOCHASTIC", "PER_GREEDY", "PER_MAX_K",
+    "metrics_workspace_bytes", "metrics_reset", "metrics_append", "metrics_auc", "METRICS_TILE",
+    "METRICS_STATE_WORDS",
     "bn_forward", "bn_backward", "td3_noise", "td3_act", "td3_smooth", "td3_critic_loss",
     "SoftUpdateTable", "soft_update_multi", "TD3_NOISE_NONE", "TD3_NOISE_PTR", "TD3_NOISE_SEED",
     "TD3_MAX_A",
@@ -1433,6 +1436,93 @@ def per_sample(memory: torch.Tensor, prio: torch.Tensor, n_valid: int, k: int, m
     lib.ctr_per_sample(N, T, n_valid, k, mode, seed, beta, _p(memory), _p(prio), _p(idx),
                        _p(batch), _p(isw), _p(min_p), _p(ws), ws.numel(), _stream())
     return out
+
+
+# --------------------------------------- evaluation metrics (csrc/metrics.hip) --------
+METRICS_TILE = 4096         # records per sort / reduce tile (ctr_metrics_tile())
+METRICS_STATE_WORDS = 16    # the state block, as int64 words (include/ctr_hip.h)
+_LABEL_TYPES = {torch.float32: CTR_LABEL_F32, torch.int32: CTR_LABEL_I32,
+                torch.int64: CTR_LABEL_I64}
+
+
+def metrics_workspace_bytes(cap: int) -> int:
+    n = lib.ctr_metrics_workspace_bytes(cap)
+    if n <= 0:
+        raise ValueError(f"metrics: capacity {cap} outside [1, 2^31)")
+    return n
+
+
+def _metrics_buffers(records: torch.Tensor, ws: torch.Tensor, state: torch.Tensor) -> int:
+    _dev(records, "records")
+    _dev(ws, "ws")
+    _dev(state, "state")
+    if records.dtype != torch.int64 or records.dim() != 1 or not records.is_contiguous():
+        raise ValueError("metrics: records must be a contiguous int64 vector")
+    if state.dtype != torch.int64 or state.numel() != METRICS_STATE_WORDS or \
+            not state.is_contiguous():
+        raise ValueError(f"metrics: state must be {METRICS_STATE_WORDS} contiguous int64 words")
+    if ws.dtype != torch.uint8 or not ws.is_contiguous():
+        raise ValueError("metrics: ws must be a contiguous uint8 buffer")
+    return records.numel()
+
+
+def _metrics_stride(t: torch.Tensor, name: str) -> int:
+    """Element stride of a float32 prediction tensor read in logical order: contiguous, a
+    [B, 1] view, or a column of a wider matrix."""
+    _dev(t, name)
+    if t.dtype != torch.float32:
+        raise TypeError(f"{name}: expected float32, got {t.dtype}")
+    if t.numel() <= 1 or t.is_contiguous():
+        return 1
+    dims = [(s, st) for s, st in zip(t.shape, t.stride()) if s != 1]
+    if len(dims) != 1 or dims[0][1] < 1:
+        raise ValueError(f"{name}: must be contiguous or a single strided column, got shape "
+                         f"{tuple(t.shape)} strides {t.stride()}")
+    return dims[0][1]
+
+
+def metrics_reset(state: torch.Tensor) -> None:
+    _dev(state, "state")
+    if state.dtype != torch.int64 or state.numel() != METRICS_STATE_WORDS or \
+            not state.is_contiguous():
+        raise ValueError(f"metrics: state must be {METRICS_STATE_WORDS} contiguous int64 words")
+    lib.ctr_metrics_reset(_p(state), _stream())
+
+
+def metrics_append(records: torch.Tensor, offset: int, y_pred: torch.Tensor,
+                   labels: torch.Tensor, rewards: torch.Tensor | None, with_loss: bool,
+                   ws: torch.Tensor, state: torch.Tensor) -> int:
+    """One batch into records[offset : offset + n] (include/ctr_hip.h, ctr_metrics_append);
+    returns n. Nothing is read back."""
+    cap = _metrics_buffers(records, ws, state)
+    stride = _metrics_stride(y_pred, "y_pred")
+    n = y_pred.numel()
+    _dev(labels, "labels")
+    if labels.dtype not in _LABEL_TYPES:
+        raise TypeError(f"labels: expected float32, int32 or int64, got {labels.dtype}")
+    if labels.numel() != n:
+        raise ValueError(f"metrics: {n} predictions but {labels.numel()} labels")
+    if not labels.is_contiguous():
+        raise ValueError("labels: must be contiguous")
+    if rewards is not None:
+        _f32(rewards, "rewards")
+        if rewards.numel() != n:
+            raise ValueError(f"metrics: {n} predictions but {rewards.numel()} rewards")
+    if offset < 0 or offset + n > cap:
+        raise ValueError(f"metrics: offset {offset} + n {n} exceeds the capacity {cap}")
+    lib.ctr_metrics_append(cap, offset, n, _p(y_pred), stride, _p(labels),
+                           _LABEL_TYPES[labels.dtype], _p(rewards), 1 if with_loss else 0,
+                           _p(records), _p(ws), ws.numel(), _p(state), _stream())
+    return n
+
+
+def metrics_auc(records: torch.Tensor, count: int, ws: torch.Tensor,
+                state: torch.Tensor) -> None:
+    """Sort records[:count] in place and leave U2, P, N in the state block."""
+    cap = _metrics_buffers(records, ws, state)
+    if not 0 <= count <= cap:
+        raise ValueError(f"metrics: count {count} outside [0, {cap}]")
+    lib.ctr_metrics_auc(cap, count, _p(records), _p(ws), ws.numel(), _p(state), _stream())
 
 
 # --------------------------------------------- hybrid TD3 agent (csrc/td3.hip) ---------

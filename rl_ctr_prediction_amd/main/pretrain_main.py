@@ -62,7 +62,9 @@ def get_dataset(datapath, dataset_name, campaign_id, valid_day, test_day):
 
 def main(data_path, dataset_name, campaign_id, valid_day, test_day, latent_dims, model_name, epoch,
          learning_rate, weight_decay, early_stop_type, batch_size, device, save_param_dir,
-         verbose=True):
+         verbose=True, metrics="host"):
+    if metrics not in ("host", "device"):
+        raise ValueError(f"metrics={metrics!r}: expected 'host' or 'device'")
     if not os.path.exists(save_param_dir + campaign_id):
         os.mkdir(save_param_dir + campaign_id)
     device = torch.device(device)
@@ -90,7 +92,7 @@ def main(data_path, dataset_name, campaign_id, valid_day, test_day, latent_dims,
         train_average_loss = train(model, trainer, train_data_loader, loss, device)
         torch.save(model.state_dict(),
                    save_param_dir + campaign_id + model_name + str(np.mod(epoch_i, 5)) + ".pth")
-        auc, valid_loss = test(model, valid_data_loader, loss, device)
+        auc, valid_loss = test(model, valid_data_loader, loss, device, metrics=metrics)
         valid_aucs.append(auc)
         valid_losses.append(valid_loss)
         history.append(dict(epoch=epoch_i, lr=learning_rate, train_loss=train_average_loss,
@@ -112,7 +114,7 @@ def main(data_path, dataset_name, campaign_id, valid_day, test_day, latent_dims,
         test_model.load_state_dict(torch.load(load_path, map_location=device, weights_only=True))
     else:
         test_model = model
-    auc, test_loss = test(test_model, test_data_loader, loss, device)
+    auc, test_loss = test(test_model, test_data_loader, loss, device, metrics=metrics)
     torch.save(test_model.state_dict(), save_param_dir + campaign_id + model_name + "best.pth")
     if verbose:
         print("\ntest auc:", auc, datetime.datetime.now(),
@@ -121,10 +123,12 @@ def main(data_path, dataset_name, campaign_id, valid_day, test_day, latent_dims,
     submission_path = data_path + dataset_name + campaign_id + model_name + "/"
     if not os.path.exists(submission_path):
         os.mkdir(submission_path)
-    valid_predicts, valid_auc = submission(test_model, valid_data_loader, device)
+    valid_predicts, valid_auc = submission(test_model, valid_data_loader, device,
+                                            metrics=metrics)
     pd.DataFrame(data=valid_predicts).to_csv(
         submission_path + str(valid_day) + "_test_submission.csv", header=None)
-    test_predicts, test_auc = submission(test_model, test_data_loader, device)
+    test_predicts, test_auc = submission(test_model, test_data_loader, device,
+                                          metrics=metrics)
     pd.DataFrame(data=test_predicts).to_csv(
         submission_path + str(test_day) + "_test_submission.csv", header=None)
     pd.DataFrame(data=[[valid_day, valid_auc], [test_day, test_auc]]).to_csv(
@@ -153,6 +157,8 @@ def _parser():
     parser.add_argument("--batch_size", type=int, default=2048)
     parser.add_argument("--device", default="cuda:0")
     parser.add_argument("--save_param_dir", default="../models/model_params/")
+    parser.add_argument("--metrics", default="host", choices=["host", "device"],
+                        help="where AUC and validation loss are computed")
     return parser
 
 
@@ -161,4 +167,5 @@ if __name__ == "__main__":
     setup_seed(1)
     main(args.data_path, args.dataset_name, args.campaign_id, args.valid_day, args.test_day,
          args.latent_dims, args.model_name, args.epoch, args.learning_rate, args.weight_decay,
-         args.early_stop_type, args.batch_size, args.device, args.save_param_dir)
+         args.early_stop_type, args.batch_size, args.device, args.save_param_dir,
+         metrics=args.metrics)

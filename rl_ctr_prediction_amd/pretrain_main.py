@@ -34,6 +34,7 @@ from . import creat_data as Data
 from .binfmt import load_encoded
 from . import p_model as Model
 from .ffm_trainer import FusedFFMTrainer
+from .metrics import DeviceMetrics
 from .trainer import FusedCTRTrainer
 
 
@@ -190,12 +191,46 @@ def _predict(model, data_loader, loss):
     return targets, predicts, total / max(intervals, 1)
 
 
-def test(model, data_loader, loss, device):
+def _check_metrics(metrics):
+    if metrics not in ("host", "device"):
+        raise ValueError(f"metrics={metrics!r}: expected 'host' or 'device'")
+    return metrics == "device"
+
+
+def _predict_device(model, data_loader, keep_predictions=False):
+    """The device counterpart of _predict: every batch goes to a DeviceMetrics accumulator
+    (one launch, no .item() / .tolist()), compute() reads the results once. Returns its dict
+    and, when asked, the predictions [N, 1] still on the device."""
+    model.eval()
+    batches = list(data_loader)  # views of the device-resident data
+    total = sum(int(labels.numel()) for _, labels in batches)
+    predicts = []
+    with torch.no_grad():
+        acc = DeviceMetrics(max(total, 1), batches[0][0].device if batches else "cuda:0")
+        for features, labels in batches:
+            y = model(features)
+            acc.add(y, labels)
+            if keep_predictions:
+                predicts.append(y)
+    res = acc.compute()
+    return res, (torch.cat(predicts) if keep_predictions else None)
+
+
+def test(model, data_loader, loss, device, metrics="host"):
+    """(auc, mean of the batch losses). metrics="host": the reference's loop (a host read per
+    batch, sklearn's AUC); "device": the same two numbers from DeviceMetrics, the AUC exact and
+    the loss summed in fp64, with one host read at the end."""
+    if _check_metrics(metrics):
+        res, _ = _predict_device(model, data_loader)
+        return res["auc"], res["loss"]
     targets, predicts, avg = _predict(model, data_loader, loss)
     return roc_auc_score(targets, predicts), avg
 
 
-def submission(model, data_loader, device):
+def submission(model, data_loader, device, metrics="host"):
+    if _check_metrics(metrics):
+        res, y = _predict_device(model, data_loader, keep_predictions=True)
+        return y.cpu().tolist(), res["auc"]  # one copy; the nested lists the CSV writer gets
     targets, predicts, _ = _predict(model, data_loader, nn.BCELoss())
     return predicts, roc_auc_score(targets, predicts)
 
@@ -216,9 +251,12 @@ def eva_stopping(valid_aucs, valid_losses, type):  # noqa: A002 (reference name)
 
 def main(data_path, dataset_name, campaign_id, latent_dims, model_name, epoch, learning_rate,
          weight_decay, early_stop_type, batch_size, device, save_param_dir, verbose=True,
-         _epoch_fn=None):
-    """_epoch_fn(model, trainer, train_fm, loss, device, batch_size) -> mean train loss: the
+         _epoch_fn=None, metrics="host"):
+    """metrics: "host" (the reference's evaluation loop, the default) or "device"
+    (DeviceMetrics: no host read per batch).
+    _epoch_fn(model, trainer, train_fm, loss, device, batch_size) -> mean train loss: the
     epoch loop of a driver variant (pretrain_main_2's slicing loop); default: DeviceBatches."""
+    _check_metrics(metrics)
     if not os.path.exists(save_param_dir + campaign_id):
         os.mkdir(save_param_dir + campaign_id)
     device = torch.device(device)
@@ -246,7 +284,7 @@ def main(data_path, dataset_name, campaign_id, latent_dims, model_name, epoch, l
             train_average_loss = _epoch_fn(model, trainer, train_fm, loss, device, batch_size)
         torch.save(model.state_dict(),
                    save_param_dir + campaign_id + model_name + str(np.mod(epoch_i, 5)) + ".pth")
-        auc, valid_loss = test(model, test_data_loader, loss, device)
+        auc, valid_loss = test(model, test_data_loader, loss, device, metrics=metrics)
         valid_aucs.append(auc)
         valid_losses.append(valid_loss)
         history.append(dict(epoch=epoch_i, train_loss=train_average_loss, valid_auc=auc,
@@ -268,7 +306,7 @@ def main(data_path, dataset_name, campaign_id, latent_dims, model_name, epoch, l
         test_model.load_state_dict(torch.load(load_path, map_location=device, weights_only=True))
     else:
         test_model = model
-    auc, test_loss = test(test_model, test_data_loader, loss, device)
+    auc, test_loss = test(test_model, test_data_loader, loss, device, metrics=metrics)
     torch.save(test_model.state_dict(), save_param_dir + campaign_id + model_name + "best.pth")
     if verbose:
         print("\ntest auc:", auc, datetime.datetime.now(),
@@ -277,7 +315,8 @@ def main(data_path, dataset_name, campaign_id, latent_dims, model_name, epoch, l
     submission_path = data_path + dataset_name + campaign_id + model_name + "/"
     if not os.path.exists(submission_path):
         os.mkdir(submission_path)
-    test_predicts, test_auc = submission(test_model, test_data_loader, device)
+    test_predicts, test_auc = submission(test_model, test_data_loader, device,
+                                          metrics=metrics)
     pd.DataFrame(data=test_predicts).to_csv(submission_path + "test_submission.csv", header=None)
     pd.DataFrame(data=[[test_auc]]).to_csv(submission_path + "day_aucs.csv", header=None)
     for i in range(5):
@@ -302,6 +341,8 @@ def _parser():
     parser.add_argument("--batch_size", type=int, default=4096)
     parser.add_argument("--device", default="cuda:0")
     parser.add_argument("--save_param_dir", default="../models/model_params/")
+    parser.add_argument("--metrics", default="host", choices=["host", "device"],
+                        help="where AUC and validation loss are computed")
     return parser
 
 
@@ -310,4 +351,4 @@ if __name__ == "__main__":
     setup_seed(1)
     main(args.data_path, args.dataset_name, args.campaign_id, args.latent_dims, args.model_name,
          args.epoch, args.learning_rate, args.weight_decay, args.early_stop_type,
-         args.batch_size, args.device, args.save_param_dir)
+         args.batch_size, args.device, args.save_param_dir, metrics=args.metrics)

@@ -43,7 +43,8 @@ def train(model, optimizer, train_data, loss, device, len_train, batch):
 
 
 def main(data_path, dataset_name, campaign_id, latent_dims, model_name, epoch, learning_rate,
-         weight_decay, early_stop_type, batch_size, device, save_param_dir, verbose=True):
+         weight_decay, early_stop_type, batch_size, device, save_param_dir, verbose=True,
+         metrics="host"):
     cache = {}
 
     def epoch_fn(model, trainer, train_fm, loss, dev, bs):
@@ -54,7 +55,7 @@ def main(data_path, dataset_name, campaign_id, latent_dims, model_name, epoch, l
 
     return _pm.main(data_path, dataset_name, campaign_id, latent_dims, model_name, epoch,
                     learning_rate, weight_decay, early_stop_type, batch_size, device,
-                    save_param_dir, verbose=verbose, _epoch_fn=epoch_fn)
+                    save_param_dir, verbose=verbose, _epoch_fn=epoch_fn, metrics=metrics)
 
 
 if __name__ == "__main__":
@@ -62,4 +63,4 @@ if __name__ == "__main__":
     setup_seed(1)
     main(args.data_path, args.dataset_name, args.campaign_id, args.latent_dims, args.model_name,
          args.epoch, args.learning_rate, args.weight_decay, args.early_stop_type,
-         args.batch_size, args.device, args.save_param_dir)
+         args.batch_size, args.device, args.save_param_dir, metrics=args.metrics)
