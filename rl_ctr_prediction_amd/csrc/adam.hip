@@ -21,8 +21,6 @@
 // (tests/test_gpu_deferred.py).
 #include "adam_common.h"
 
-#include <cstdlib>
-
 namespace ctr {
 
 // (adam_replay_vec, the replay step of an absent row, is in adam_common.h. Measured and
@@ -449,6 +447,11 @@ constexpr int kMaxLdsSteps = 8192;  // 64 KiB of float2
 // replay of the batch's rows runs as one step loop over all of them (4 x UNR independent
 // chains per lane). Tiles whose rows are all current are skipped on one vote; last[] is
 // written back coalesced. Same adam_elem, same per-step scalars: bitwise the old pass.
+// (Tried, bitwise, slower, removed: a software-pipelined flush that kept the next batch's
+// loads in flight under the current batch's replay, two register buffers of UNR = 2 rows.
+// C3 table 4.62-4.68 vs 4.28-4.32 ms at 20 replayed steps, 8.14-8.29 vs 7.26-7.50 at 40,
+// grids 512-4096 no better: the flush is arithmetic-bound there — VALU busy ~95 % of SIMD
+// cycles — not waiting on its loads, and the replay per step costs more at UNR = 2.)
 template <int K4, int UNR, bool LDS_TAB>
 __global__ __launch_bounds__(256) void deferred_flush_tile(
     float4* __restrict__ E, float4* __restrict__ mE, float4* __restrict__ vE,
@@ -523,149 +526,6 @@ __global__ __launch_bounds__(256) void deferred_flush_tile(
         }
     }
     if (from_l < step) last[my] = step;
-  }
-}
-
-// The flush, software-pipelined (build option CTR_FLUSH_PIPE=1, K4 >= 8; measured slower,
-// kept for the record). The tile kernel's waves each load a batch, replay it, store it;
-// at 20 replayed steps the flush measured close to the SUM of its row traffic and its replay
-// (C3 table: 3.09 ms at 1 step, 4.33 at 20, 7.22 at 40), which suggested waves of a SIMD
-// falling into step. Here each wave keeps the NEXT batch's loads in flight while it replays
-// the current one: two register buffers of UNR float4 rows (UNR = 2 keeps four waves per
-// SIMD at K = 64). Loads are unconditional — a row already current reads row 0's cached
-// columns instead — so the compiler's in-order vmcnt counting waits for the current buffer
-// only; stores stay predicated. A tile's NB batches are unrolled, the first batch of the
-// next tile (and its rows' last[] / linear state, one tile ahead) is issued under the
-// current tile's last batch; the linear weight's chain rides in the replay loop of a
-// tile's first batch. Bitwise the tile kernel (tests/test_gpu_deferred.py), but slower:
-// C3 table 4.62-4.68 vs 4.28-4.32 ms at 20 steps, 8.14-8.29 vs 7.26-7.50 at 40 (grids
-// 512-4096 no better) — the replay per step costs more at UNR = 2, and the flush's
-// counters (r02_flush_pmc.txt: VALU busy ~95 % of SIMD cycles at 20 steps, at ~1.8 GHz)
-// say it is arithmetic-bound there, not waiting on its loads.
-#ifndef CTR_FLUSH_PIPE
-#define CTR_FLUSH_PIPE 0
-#endif
-#ifndef CTR_FLUSH_PIPE_UNR
-#define CTR_FLUSH_PIPE_UNR 2
-#endif
-
-template <int UNR>
-struct FlushBatch {
-  float4 p[UNR], m[UNR], v[UNR];
-  int from[UNR];
-  int64_t e[UNR];
-};
-
-struct FlushTileMeta {  // the lane's own row of a tile: last[] and the linear weight's state
-  int fl;
-  float lp, lm, lv;
-};
-
-template <int K4, int UNR, bool LDS_TAB>
-__global__ __launch_bounds__(256) void deferred_flush_pipe(
-    float4* __restrict__ E, float4* __restrict__ mE, float4* __restrict__ vE,
-    float* __restrict__ w, float* __restrict__ mw, float* __restrict__ vw, int64_t V,
-    int32_t* __restrict__ last, int step, const float* __restrict__ tab, AdamHP h) {
-  extern __shared__ __attribute__((aligned(16))) float2 s_tab[];
-  if (LDS_TAB) {
-    for (int i = threadIdx.x; i <= step; i += blockDim.x)
-      s_tab[i] = reinterpret_cast<const float2*>(tab)[i];
-    __syncthreads();
-  }
-  constexpr int RPI = kWave / K4;  // rows per wave-instruction
-  constexpr int NB = K4 / UNR;     // batches per 64-row tile
-  static_assert(K4 % UNR == 0 && NB % 2 == 0, "an even number of batches per tile");
-  const int lane = threadIdx.x & (kWave - 1);
-  const int c = lane % K4, r_in = lane / K4;
-  const int64_t waves = (int64_t)gridDim.x * (blockDim.x / kWave);
-  const int64_t n_tiles = (V + kWave - 1) / kWave;
-  const int64_t t_first = (int64_t)blockIdx.x * (blockDim.x / kWave) + threadIdx.x / kWave;
-  if (t_first >= n_tiles) return;  // wave-uniform, after the block's only barrier
-  const int64_t t_last = t_first + (n_tiles - 1 - t_first) / waves * waves;
-  auto set_step = [&](int t) {
-    if (LDS_TAB) {
-      const float2 v = s_tab[t];
-      h.neg_step_size = v.x;
-      h.inv_bc2_sqrt = v.y;
-    } else {
-      load_step(h, tab, t);
-    }
-  };
-  auto load_meta = [&](int64_t tile, FlushTileMeta& M) {
-    const int64_t my = tile * kWave + lane;
-    const bool ok = my < V;
-    const int64_t ms = ok ? my : 0;  // clamped: every lane loads a valid address
-    const int f = last[ms];
-    M.fl = ok ? f : step;            // lanes past V read as current
-    if (w) {
-      M.lp = w[ms];
-      M.lm = mw[ms];
-      M.lv = vw[ms];
-    }
-  };
-  auto issue = [&](int64_t tile, int bi, const FlushTileMeta& M, FlushBatch<UNR>& X) {
-    const int64_t base = tile * kWave;
-#pragma unroll
-    for (int u = 0; u < UNR; ++u) {
-      const int r = (bi * UNR + u) * RPI + r_in;
-      X.from[u] = __shfl(M.fl, r, kWave);
-      X.e[u] = (base + r) * K4 + c;
-      const int64_t el = X.from[u] < step ? X.e[u] : c;  // current rows: row 0, cached
-      X.p[u] = E[el];
-      X.m[u] = mE[el];
-      X.v[u] = vE[el];
-    }
-  };
-  auto replay_store = [&](int64_t tile, bool first, FlushTileMeta& M, FlushBatch<UNR>& X) {
-    int f0 = step;
-#pragma unroll
-    for (int u = 0; u < UNR; ++u) f0 = min(f0, X.from[u]);
-    const int fl_lin = (first && w) ? M.fl : step;
-    f0 = min(f0, fl_lin);
-    for (int s = f0 + 1; s <= step; ++s) {
-      set_step(s);
-      if (s > fl_lin) adam_elem(M.lp, 0.f, M.lm, M.lv, h);
-#pragma unroll
-      for (int u = 0; u < UNR; ++u)
-        if (s > X.from[u]) adam_replay_vec(X.p[u], X.m[u], X.v[u], h);
-    }
-#pragma unroll
-    for (int u = 0; u < UNR; ++u)
-      if (X.from[u] < step) {
-        E[X.e[u]] = X.p[u];
-        mE[X.e[u]] = X.m[u];
-        vE[X.e[u]] = X.v[u];
-      }
-    if (first && M.fl < step) {  // fl < step only for rows below V
-      const int64_t my = tile * kWave + lane;
-      if (w) {
-        w[my] = M.lp;
-        mw[my] = M.lm;
-        vw[my] = M.lv;
-      }
-      last[my] = step;
-    }
-  };
-  FlushBatch<UNR> X0, X1;
-  FlushTileMeta cur, nxt;
-  load_meta(t_first, cur);
-  load_meta(t_first + waves <= t_last ? t_first + waves : t_last, nxt);
-  issue(t_first, 0, cur, X0);
-  for (int64_t tile = t_first; tile <= t_last; tile += waves) {
-    const int64_t nt = tile + waves <= t_last ? tile + waves : t_last;  // clamped: the last
-    // tile's prefetch re-reads a batch it never replays
-#pragma unroll
-    for (int bi = 0; bi < NB; ++bi) {
-      FlushBatch<UNR>& now = (bi & 1) ? X1 : X0;
-      FlushBatch<UNR>& ahead = (bi & 1) ? X0 : X1;
-      if (bi + 1 < NB)
-        issue(tile, bi + 1, cur, ahead);
-      else
-        issue(nt, 0, nxt, ahead);
-      replay_store(tile, bi == 0, cur, now);
-    }
-    cur = nxt;
-    load_meta(nt + waves <= t_last ? nt + waves : t_last, nxt);
   }
 }
 
@@ -813,22 +673,13 @@ extern "C" int ctr_adam_embedding(float* emb, float* m_emb, float* v_emb, float*
   if (K % 4 == 0 && al && K4 <= 64 && (kWave % K4) == 0) {
     const int64_t n_tiles = ceil_div(V, kWave);
     const unsigned grid = (unsigned)std::min<int64_t>(ceil_div(n_tiles, 4), 8192);
-#define CTR_ADAM_VEC(K4_)                                                                     \
-  hipLaunchKernelGGL((adam_embedding_vec<K4_>), grid, 256, 0, st,                             \
-                     reinterpret_cast<float4*>(emb), reinterpret_cast<float4*>(m_emb),        \
-                     reinterpret_cast<float4*>(v_emb), lin, m_lin, v_lin, V, rowmap,          \
-                     reinterpret_cast<const float4*>(grad_rows), grad_lin, h, step_table,      \
-                     step_ptr)
-    switch (K4) {
-      case 1: CTR_ADAM_VEC(1); break;
-      case 2: CTR_ADAM_VEC(2); break;
-      case 4: CTR_ADAM_VEC(4); break;
-      case 8: CTR_ADAM_VEC(8); break;
-      case 16: CTR_ADAM_VEC(16); break;
-      case 32: CTR_ADAM_VEC(32); break;
-      case 64: CTR_ADAM_VEC(64); break;
-    }
-#undef CTR_ADAM_VEC
+    dispatch_width(K4, [&](auto k4) {
+      hipLaunchKernelGGL((adam_embedding_vec<decltype(k4)::value>), grid, 256, 0, st,
+                         reinterpret_cast<float4*>(emb), reinterpret_cast<float4*>(m_emb),
+                         reinterpret_cast<float4*>(v_emb), lin, m_lin, v_lin, V, rowmap,
+                         reinterpret_cast<const float4*>(grad_rows), grad_lin, h, step_table,
+                         step_ptr);
+    });
     CTR_LAUNCH_CHECK("adam_embedding_vec");
     return CTR_OK;
   }
@@ -933,63 +784,73 @@ static bool deferred_vec_ok(int K, const void* a, const void* b, const void* c, 
          ((uintptr_t)a | (uintptr_t)b | (uintptr_t)c | (uintptr_t)g) % 16 == 0;
 }
 
+// The tables of a deferred entry point as its launches pass them (host side only: the
+// kernels take the pointers one by one, each __restrict__), with the hyper-parameters;
+// the per-step scalars come from the step table.
+struct DeferredTables {
+  float4 *E, *mE, *vE;
+  float *w, *mw, *vw;
+  int32_t* last;
+  AdamHP h;
+};
+
+// Fills the view and runs the checks every deferred entry point shares. who: the entry
+// point's name; ranges_ok: its own bounds on step, S and V, reported with V > 0 and K > 0
+// as "bad sizes".
+static int deferred_tables(DeferredTables& t, const char* who, float* emb, float* m_emb,
+                           float* v_emb, float* lin, float* m_lin, float* v_lin, int64_t V, int K,
+                           int32_t* last, const float* step_table, bool ranges_ok, double beta1,
+                           double beta2, double eps, double weight_decay) {
+  CTR_REQUIRE(emb && m_emb && v_emb && last && step_table, "%s: null pointer", who);
+  CTR_REQUIRE(V > 0 && K > 0 && ranges_ok, "%s: bad sizes", who);
+  CTR_REQUIRE((lin && m_lin && v_lin) || (!lin && !m_lin && !v_lin),
+              "%s: linear table pointers must be all set or all NULL", who);
+  t = {reinterpret_cast<float4*>(emb), reinterpret_cast<float4*>(m_emb),
+       reinterpret_cast<float4*>(v_emb), lin, m_lin, v_lin, last,
+       make_hp(1.0, 1.0, beta1, beta2, eps, weight_decay)};
+  return CTR_OK;
+}
+
 extern "C" int ctr_adam_deferred_rows(float* emb, float* m_emb, float* v_emb, float* lin,
                                       float* m_lin, float* v_lin, int64_t V, int K, int32_t* last,
                                       const ctr_sparse_plan* plan, const float* grad_rows,
                                       const float* grad_lin, int64_t step, const int32_t* step_ptr,
                                       const float* step_table, double beta1, double beta2,
                                       double eps, double weight_decay, ctr_stream_t stream) {
-  CTR_REQUIRE(emb && m_emb && v_emb && last && step_table, "ctr_adam_deferred_rows: null pointer");
+  DeferredTables t;
+  const int rc = deferred_tables(t, "ctr_adam_deferred_rows", emb, m_emb, v_emb, lin, m_lin, v_lin,
+                                 V, K, last, step_table,
+                                 step_ptr || (step >= 1 && step < (int64_t(1) << 31)), beta1,
+                                 beta2, eps, weight_decay);
+  if (rc != CTR_OK) return rc;
   CTR_REQUIRE(plan && plan->unique_rows && plan->num_unique, "ctr_adam_deferred_rows: bad plan");
-  CTR_REQUIRE(V > 0 && K > 0 && (step_ptr || (step >= 1 && step < (int64_t(1) << 31))),
-              "ctr_adam_deferred_rows: bad sizes");
-  CTR_REQUIRE((lin && m_lin && v_lin) || (!lin && !m_lin && !v_lin),
-              "ctr_adam_deferred_rows: linear table pointers must be all set or all NULL");
   CTR_REQUIRE(!grad_rows || !lin || grad_lin, "ctr_adam_deferred_rows: grad_lin missing");
   if (plan->S == 0) return CTR_OK;
-  const AdamHP h = make_hp(1.0, 1.0, beta1, beta2, eps, weight_decay);
   hipStream_t st = as_stream(stream);
   const bool apply = grad_rows != nullptr;
+  const float* glin = apply ? grad_lin : nullptr;  // a catch-up takes no gradient
   const int64_t n = plan->S;  // upper bound on unique rows
   if (deferred_vec_ok(K, emb, m_emb, v_emb, grad_rows)) {
     const int K4 = K / 4;
     const unsigned grid = (unsigned)std::max<int64_t>(1, std::min<int64_t>(ceil_div(n * K4, 256), 8192));
-#define CTR_DEF_ROWS(K4_)                                                                        \
-  if (apply)                                                                                     \
-    hipLaunchKernelGGL((deferred_rows_vec<K4_, true>), grid, 256, 0, st,                         \
-                       reinterpret_cast<float4*>(emb), reinterpret_cast<float4*>(m_emb),         \
-                       reinterpret_cast<float4*>(v_emb), lin, m_lin, v_lin, last,                \
-                       plan->unique_rows, plan->num_unique,                                      \
-                       reinterpret_cast<const float4*>(grad_rows), grad_lin, (int)step,          \
-                       step_ptr, step_table, h);                                                 \
-  else                                                                                           \
-    hipLaunchKernelGGL((deferred_rows_vec<K4_, false>), grid, 256, 0, st,                        \
-                       reinterpret_cast<float4*>(emb), reinterpret_cast<float4*>(m_emb),         \
-                       reinterpret_cast<float4*>(v_emb), lin, m_lin, v_lin, last,                \
-                       plan->unique_rows, plan->num_unique, nullptr, nullptr, (int)step,         \
-                       step_ptr, step_table, h)
-    switch (K4) {
-      case 1: CTR_DEF_ROWS(1); break;
-      case 2: CTR_DEF_ROWS(2); break;
-      case 4: CTR_DEF_ROWS(4); break;
-      case 8: CTR_DEF_ROWS(8); break;
-      case 16: CTR_DEF_ROWS(16); break;
-      case 32: CTR_DEF_ROWS(32); break;
-      case 64: CTR_DEF_ROWS(64); break;
-    }
-#undef CTR_DEF_ROWS
+    dispatch_width(K4, [&](auto k4) {
+      dispatch_bool(apply, [&](auto ap) {
+        hipLaunchKernelGGL((deferred_rows_vec<decltype(k4)::value, decltype(ap)::value>), grid,
+                           256, 0, st, t.E, t.mE, t.vE, t.w, t.mw, t.vw, t.last,
+                           plan->unique_rows, plan->num_unique,
+                           reinterpret_cast<const float4*>(grad_rows), glin, (int)step, step_ptr,
+                           step_table, t.h);
+      });
+    });
     CTR_LAUNCH_CHECK("deferred_rows_vec");
     return CTR_OK;
   }
   const unsigned grid = (unsigned)std::max<int64_t>(1, std::min<int64_t>(ceil_div(n, 256), 8192));
-  if (apply)
-    hipLaunchKernelGGL(deferred_scalar<true>, grid, 256, 0, st, emb, m_emb, v_emb, lin, m_lin,
-                       v_lin, n, K, last, plan->unique_rows, plan->num_unique, grad_rows, grad_lin,
-                       (int)step, step_ptr, step_table, h);
-  else
-    hipLaunchKernelGGL(deferred_scalar<false>, grid, 256, 0, st, emb, m_emb, v_emb, lin, m_lin,
-                       v_lin, n, K, last, plan->unique_rows, plan->num_unique, nullptr, nullptr,
-                       (int)step, step_ptr, step_table, h);
+  dispatch_bool(apply, [&](auto ap) {
+    hipLaunchKernelGGL(deferred_scalar<decltype(ap)::value>, grid, 256, 0, st, emb, m_emb, v_emb,
+                       lin, m_lin, v_lin, n, K, last, plan->unique_rows, plan->num_unique,
+                       grad_rows, glin, (int)step, step_ptr, step_table, t.h);
+  });
   CTR_LAUNCH_CHECK("deferred_scalar");
   return CTR_OK;
 }
@@ -1003,14 +864,17 @@ extern "C" int ctr_adam_deferred_entries(float* emb, float* m_emb, float* v_emb,
                                          const float* step_table, double beta1, double beta2,
                                          double eps, double weight_decay, float* out,
                                          float* out_lin, ctr_stream_t stream) {
-  CTR_REQUIRE(emb && m_emb && v_emb && last && step_table && vals,
-              "ctr_adam_deferred_entries: null pointer");
+  CTR_REQUIRE(vals, "ctr_adam_deferred_entries: null pointer");
+  DeferredTables t;
+  const int rc = deferred_tables(t, "ctr_adam_deferred_entries", emb, m_emb, v_emb, lin, m_lin,
+                                 v_lin, V, K, last, step_table,
+                                 step_ptr || (step >= 1 && step < (int64_t(1) << 31)), beta1,
+                                 beta2, eps, weight_decay);
+  if (rc != CTR_OK) return rc;
   CTR_REQUIRE(plan && plan->unique_rows && plan->num_unique && plan->seg_offsets &&
                   plan->sorted_slots,
               "ctr_adam_deferred_entries: bad plan");
-  CTR_REQUIRE(V > 0 && K > 0 && (step_ptr || (step >= 1 && step < (int64_t(1) << 31))),
-              "ctr_adam_deferred_entries: bad sizes");
-  CTR_REQUIRE((lin && m_lin && v_lin && (vals_lin || run_len > 0)) || (!lin && !m_lin && !v_lin),
+  CTR_REQUIRE(!lin || vals_lin || run_len > 0,
               "ctr_adam_deferred_entries: linear table pointers (and vals_lin) all set or all NULL");
   CTR_REQUIRE(run_len >= 0 && (run_len == 0 || (chunk % 4 == 0 &&
                                                  chunk >= run_len * K + (lin ? run_len : 0))),
@@ -1018,28 +882,17 @@ extern "C" int ctr_adam_deferred_entries(float* emb, float* m_emb, float* v_emb,
   CTR_REQUIRE(deferred_vec_ok(K, emb, m_emb, v_emb, vals) && (!out || (uintptr_t)out % 16 == 0),
               "ctr_adam_deferred_entries: needs K %% 4 == 0, (K/4) | 64 and 16-B aligned rows");
   if (plan->S == 0) return CTR_OK;
-  const AdamHP h = make_hp(1.0, 1.0, beta1, beta2, eps, weight_decay);
   const int K4 = K / 4;
   const int64_t n = plan->S;  // upper bound on unique rows
   const unsigned grid = (unsigned)std::max<int64_t>(1, std::min<int64_t>(ceil_div(n * K4, 256), 8192));
-#define CTR_DEF_ENTRIES(K4_)                                                                    \
-  hipLaunchKernelGGL((deferred_entries_vec<K4_>), grid, 256, 0, as_stream(stream),              \
-                     reinterpret_cast<float4*>(emb), reinterpret_cast<float4*>(m_emb),          \
-                     reinterpret_cast<float4*>(v_emb), lin, m_lin, v_lin, last,                 \
-                     plan->unique_rows, plan->num_unique, plan->seg_offsets, plan->sorted_slots, \
-                     reinterpret_cast<const float4*>(vals), vals_lin, run_len, chunk, skip_row, \
-                     (int)step,                                                                  \
-                     step_ptr, step_table, h, reinterpret_cast<float4*>(out), out_lin)
-  switch (K4) {
-    case 1: CTR_DEF_ENTRIES(1); break;
-    case 2: CTR_DEF_ENTRIES(2); break;
-    case 4: CTR_DEF_ENTRIES(4); break;
-    case 8: CTR_DEF_ENTRIES(8); break;
-    case 16: CTR_DEF_ENTRIES(16); break;
-    case 32: CTR_DEF_ENTRIES(32); break;
-    case 64: CTR_DEF_ENTRIES(64); break;
-  }
-#undef CTR_DEF_ENTRIES
+  dispatch_width(K4, [&](auto k4) {
+    hipLaunchKernelGGL((deferred_entries_vec<decltype(k4)::value>), grid, 256, 0,
+                       as_stream(stream), t.E, t.mE, t.vE, t.w, t.mw, t.vw, t.last,
+                       plan->unique_rows, plan->num_unique, plan->seg_offsets, plan->sorted_slots,
+                       reinterpret_cast<const float4*>(vals), vals_lin, run_len, chunk, skip_row,
+                       (int)step, step_ptr, step_table, t.h, reinterpret_cast<float4*>(out),
+                       out_lin);
+  });
   CTR_LAUNCH_CHECK("deferred_entries_vec");
   return CTR_OK;
 }
@@ -1049,13 +902,13 @@ extern "C" int ctr_adam_deferred_flush(float* emb, float* m_emb, float* v_emb, f
                                        int64_t step, const float* step_table, double beta1,
                                        double beta2, double eps, double weight_decay,
                                        ctr_stream_t stream) {
-  CTR_REQUIRE(emb && m_emb && v_emb && last && step_table, "ctr_adam_deferred_flush: null pointer");
-  CTR_REQUIRE(V > 0 && K > 0 && step >= 0 && step < (int64_t(1) << 31),
-              "ctr_adam_deferred_flush: bad sizes");
-  CTR_REQUIRE((lin && m_lin && v_lin) || (!lin && !m_lin && !v_lin),
-              "ctr_adam_deferred_flush: linear table pointers must be all set or all NULL");
+  DeferredTables t;
+  const int rc = deferred_tables(t, "ctr_adam_deferred_flush", emb, m_emb, v_emb, lin, m_lin,
+                                 v_lin, V, K, last, step_table,
+                                 step >= 0 && step < (int64_t(1) << 31), beta1, beta2, eps,
+                                 weight_decay);
+  if (rc != CTR_OK) return rc;
   if (step == 0) return CTR_OK;
-  const AdamHP h = make_hp(1.0, 1.0, beta1, beta2, eps, weight_decay);
   hipStream_t st = as_stream(stream);
   if (deferred_vec_ok(K, emb, m_emb, v_emb, nullptr)) {
     const int K4 = K / 4;
@@ -1063,72 +916,25 @@ extern "C" int ctr_adam_deferred_flush(float* emb, float* m_emb, float* v_emb, f
     const unsigned grid = (unsigned)std::max<int64_t>(1, std::min<int64_t>(ceil_div(n_tiles, 4), 8192));
     const bool lds = step < kMaxLdsSteps;
     const size_t lds_bytes = lds ? (size_t)(step + 1) * sizeof(float2) : 0;
-    if (CTR_FLUSH_PIPE && K4 >= 8) {
-      // one generation of resident waves less a little (a wave's first batch is its only
-      // unhidden load): 256 CUs x 4 blocks of 4 waves at <= 128 VGPRs; CTR_FLUSH_GRID tunes
-      static const int64_t pipe_grid = [] {
-        const char* s = std::getenv("CTR_FLUSH_GRID");
-        return s ? std::max<int64_t>(1, std::atoll(s)) : int64_t(1024);
-      }();
-      const unsigned pgrid = (unsigned)std::max<int64_t>(1, std::min<int64_t>(ceil_div(n_tiles, 4), pipe_grid));
-#define CTR_DEF_PIPE(K4_)                                                                     \
-  if (lds)                                                                                    \
-    hipLaunchKernelGGL((deferred_flush_pipe<K4_, CTR_FLUSH_PIPE_UNR, true>), pgrid, 256,      \
-                       lds_bytes, st, reinterpret_cast<float4*>(emb),                         \
-                       reinterpret_cast<float4*>(m_emb), reinterpret_cast<float4*>(v_emb), lin, \
-                       m_lin, v_lin, V, last, (int)step, step_table, h);                      \
-  else                                                                                        \
-    hipLaunchKernelGGL((deferred_flush_pipe<K4_, CTR_FLUSH_PIPE_UNR, false>), pgrid, 256, 0,  \
-                       st, reinterpret_cast<float4*>(emb), reinterpret_cast<float4*>(m_emb),  \
-                       reinterpret_cast<float4*>(v_emb), lin, m_lin, v_lin, V, last,          \
-                       (int)step, step_table, h)
-      switch (K4) {
-        case 8: CTR_DEF_PIPE(8); break;
-        case 16: CTR_DEF_PIPE(16); break;
-        case 32: CTR_DEF_PIPE(32); break;
-        case 64: CTR_DEF_PIPE(64); break;
-      }
-#undef CTR_DEF_PIPE
-      CTR_LAUNCH_CHECK("deferred_flush_pipe");
-      return CTR_OK;
-    }
-#define CTR_DEF_FLUSH(K4_, UNR_)                                                           \
-  if (lds)                                                                                      \
-    hipLaunchKernelGGL((deferred_flush_tile<K4_, UNR_, true>), grid, 256, lds_bytes, st,        \
-                       reinterpret_cast<float4*>(emb), reinterpret_cast<float4*>(m_emb),        \
-                       reinterpret_cast<float4*>(v_emb), lin, m_lin, v_lin, V, last, (int)step, \
-                       step_table, h);                                                          \
-  else                                                                                          \
-    hipLaunchKernelGGL((deferred_flush_tile<K4_, UNR_, false>), grid, 256, 0, st,               \
-                       reinterpret_cast<float4*>(emb), reinterpret_cast<float4*>(m_emb),        \
-                       reinterpret_cast<float4*>(v_emb), lin, m_lin, v_lin, V, last, (int)step, \
-                       step_table, h)
-    switch (K4) {
-      case 1: CTR_DEF_FLUSH(1, 1); break;
-      case 2: CTR_DEF_FLUSH(2, 2); break;
-      case 4: CTR_DEF_FLUSH(4, 4); break;
-      case 8: CTR_DEF_FLUSH(8, CTR_FLUSH_UNR); break;
-      case 16: CTR_DEF_FLUSH(16, CTR_FLUSH_UNR); break;
-      case 32: CTR_DEF_FLUSH(32, CTR_FLUSH_UNR); break;
-      case 64: CTR_DEF_FLUSH(64, CTR_FLUSH_UNR); break;
-    }
-#undef CTR_DEF_FLUSH
+    dispatch_width(K4, [&](auto k4) {
+      constexpr int K4_ = decltype(k4)::value;
+      constexpr int UNR = K4_ <= 4 ? K4_ : CTR_FLUSH_UNR;  // a narrow tile is one batch
+      dispatch_bool(lds, [&](auto lds_tab) {
+        hipLaunchKernelGGL((deferred_flush_tile<K4_, UNR, decltype(lds_tab)::value>), grid, 256,
+                           lds_bytes, st, t.E, t.mE, t.vE, t.w, t.mw, t.vw, V, t.last, (int)step,
+                           step_table, t.h);
+      });
+    });
     CTR_LAUNCH_CHECK("deferred_flush_tile");
     return CTR_OK;
   }
   const unsigned grid = (unsigned)std::min<int64_t>(ceil_div(V, 256), 8192);
   hipLaunchKernelGGL(deferred_scalar<false>, grid, 256, 0, st, emb, m_emb, v_emb, lin, m_lin,
                      v_lin, V, K, last, nullptr, nullptr, nullptr, nullptr, (int)step, nullptr,
-                     step_table, h);
+                     step_table, t.h);
   CTR_LAUNCH_CHECK("deferred_flush_scalar");
   return CTR_OK;
 }
-
-static int launch_catchup_wave(float* emb, float* m_emb, float* v_emb, float* lin, float* m_lin,
-                               float* v_lin, int64_t V, int K, int32_t* last, const void* idx,
-                               int idx_type, int64_t S, const int32_t* owner,
-                               const int32_t* step_ptr, const float* step_table, AdamHP h,
-                               hipStream_t st, int64_t max_blocks = 8192);
 
 extern "C" int ctr_adam_deferred_catchup_ids(float* emb, float* m_emb, float* v_emb, float* lin,
                                              float* m_lin, float* v_lin, int64_t V, int K,
@@ -1137,17 +943,17 @@ extern "C" int ctr_adam_deferred_catchup_ids(float* emb, float* m_emb, float* v_
                                              const float* step_table, double beta1, double beta2,
                                              double eps, double weight_decay,
                                              ctr_stream_t stream) {
-  CTR_REQUIRE(emb && m_emb && v_emb && last && owner && step_ptr && step_table,
-              "ctr_adam_deferred_catchup_ids: null pointer");
-  CTR_REQUIRE(V > 0 && V < (int64_t(1) << 31) && K > 0 && S >= 0 && S < (int64_t(1) << 31),
-              "ctr_adam_deferred_catchup_ids: bad sizes");
-  CTR_REQUIRE((lin && m_lin && v_lin) || (!lin && !m_lin && !v_lin),
-              "ctr_adam_deferred_catchup_ids: linear table pointers must be all set or all NULL");
+  CTR_REQUIRE(owner && step_ptr, "ctr_adam_deferred_catchup_ids: null pointer");
+  DeferredTables t;
+  const int rc = deferred_tables(t, "ctr_adam_deferred_catchup_ids", emb, m_emb, v_emb, lin, m_lin,
+                                 v_lin, V, K, last, step_table,
+                                 V < (int64_t(1) << 31) && S >= 0 && S < (int64_t(1) << 31), beta1,
+                                 beta2, eps, weight_decay);
+  if (rc != CTR_OK) return rc;
   CTR_REQUIRE(idx_type == CTR_IDX_I32 || idx_type == CTR_IDX_I64, "bad idx_type %d", idx_type);
   CTR_REQUIRE(deferred_vec_ok(K, emb, m_emb, v_emb, nullptr),
               "ctr_adam_deferred_catchup_ids: needs K %% 4 == 0, (K/4) | 64 and 16-B rows");
   if (S == 0) return CTR_OK;
-  const AdamHP h = make_hp(1.0, 1.0, beta1, beta2, eps, weight_decay);
   hipStream_t st = as_stream(stream);
   const unsigned gm = (unsigned)std::min<int64_t>(ceil_div(S, 256), 4096);
   if (idx_type == CTR_IDX_I64)
@@ -1157,41 +963,20 @@ extern "C" int ctr_adam_deferred_catchup_ids(float* emb, float* m_emb, float* v_
     hipLaunchKernelGGL(deferred_mark_kernel<int32_t>, gm, 256, 0, st,
                        static_cast<const int32_t*>(idx), S, V, owner);
   CTR_LAUNCH_CHECK("deferred_mark_kernel");
-  return launch_catchup_wave(emb, m_emb, v_emb, lin, m_lin, v_lin, V, K, last, idx, idx_type, S,
-                             owner, step_ptr, step_table, h, st);
-}
-
-static int launch_catchup_wave(float* emb, float* m_emb, float* v_emb, float* lin, float* m_lin,
-                               float* v_lin, int64_t V, int K, int32_t* last, const void* idx,
-                               int idx_type, int64_t S, const int32_t* owner,
-                               const int32_t* step_ptr, const float* step_table, AdamHP h,
-                               hipStream_t st, int64_t max_blocks) {
-  const int K4 = K / 4;
   // one lane per slot: S / 256 blocks of 4 waves (a wave re-loops when S exceeds the grid)
-  const unsigned grid =
-      (unsigned)std::max<int64_t>(1, std::min<int64_t>(ceil_div(S, 256), max_blocks));
-#define CTR_CATCHUP(IT, K4_)                                                                   \
-  hipLaunchKernelGGL((deferred_catchup_wave<IT, K4_, 2>), grid, 256, 0, st,                    \
-                     reinterpret_cast<float4*>(emb), reinterpret_cast<float4*>(m_emb),         \
-                     reinterpret_cast<float4*>(v_emb), lin, m_lin, v_lin, last,                \
-                     static_cast<const IT*>(idx), S, V, owner, step_ptr, step_table, h)
-#define CTR_CATCHUP_K(IT)                  \
-  switch (K4) {                            \
-    case 1: CTR_CATCHUP(IT, 1); break;     \
-    case 2: CTR_CATCHUP(IT, 2); break;     \
-    case 4: CTR_CATCHUP(IT, 4); break;     \
-    case 8: CTR_CATCHUP(IT, 8); break;     \
-    case 16: CTR_CATCHUP(IT, 16); break;   \
-    case 32: CTR_CATCHUP(IT, 32); break;   \
-    case 64: CTR_CATCHUP(IT, 64); break;   \
-  }
-  if (idx_type == CTR_IDX_I64) {
-    CTR_CATCHUP_K(int64_t)
-  } else {
-    CTR_CATCHUP_K(int32_t)
-  }
-#undef CTR_CATCHUP_K
-#undef CTR_CATCHUP
+  const unsigned grid = (unsigned)std::max<int64_t>(1, std::min<int64_t>(ceil_div(S, 256), 8192));
+  dispatch_width(K / 4, [&](auto k4) {
+    auto launch = [&](auto id) {  // id: a value of the index type
+      using IdxT = decltype(id);
+      hipLaunchKernelGGL((deferred_catchup_wave<IdxT, decltype(k4)::value, 2>), grid, 256, 0, st,
+                         t.E, t.mE, t.vE, t.w, t.mw, t.vw, t.last, static_cast<const IdxT*>(idx),
+                         S, V, owner, step_ptr, step_table, t.h);
+    };
+    if (idx_type == CTR_IDX_I64)
+      launch(int64_t{});
+    else
+      launch(int32_t{});
+  });
   CTR_LAUNCH_CHECK("deferred_catchup_wave");
   return CTR_OK;
 }

@@ -6,6 +6,8 @@
 #include <stdio.h>
 #include <string.h>
 
+#include <type_traits>
+
 #include "../../include/ctr_hip.h"
 
 namespace ctr {
@@ -45,6 +47,34 @@ inline hipStream_t as_stream(ctr_stream_t s) { return reinterpret_cast<hipStream
 
 inline int64_t ceil_div(int64_t a, int64_t b) { return (a + b - 1) / b; }
 inline int64_t align_up(int64_t a, int64_t b) { return ceil_div(a, b) * b; }
+
+// ------------------------------------------------------------- template dispatch ------
+// The row kernels are instantiated per width (float4 columns or lanes of a row: K/4 in
+// {1, 2, 4, ..., 64}). A launcher writes its launch once, in a generic lambda that takes the
+// width as a std::integral_constant; false: n is none of the widths, f was not called.
+// Forced inline: the entry point holds the switch and its launches, as if written out.
+template <typename F>
+__host__ __forceinline__ bool dispatch_width(int n, F&& f) {
+  switch (n) {
+    case 1: f(std::integral_constant<int, 1>{}); return true;
+    case 2: f(std::integral_constant<int, 2>{}); return true;
+    case 4: f(std::integral_constant<int, 4>{}); return true;
+    case 8: f(std::integral_constant<int, 8>{}); return true;
+    case 16: f(std::integral_constant<int, 16>{}); return true;
+    case 32: f(std::integral_constant<int, 32>{}); return true;
+    case 64: f(std::integral_constant<int, 64>{}); return true;
+  }
+  return false;
+}
+
+// a bool template argument, the same way: f(std::true_type{}) or f(std::false_type{})
+template <typename F>
+__host__ __forceinline__ void dispatch_bool(bool b, F&& f) {
+  if (b)
+    f(std::true_type{});
+  else
+    f(std::false_type{});
+}
 
 // ------------------------------------------------------------------ index loads ------
 // Feature ids arrive as int64 (the reference's LongTensor) or int32. An id outside

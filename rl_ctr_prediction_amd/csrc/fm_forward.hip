@@ -327,31 +327,21 @@ static int launch_fm_forward(const IdxT* idx, int64_t B, int F, int K, int64_t V
                       (reinterpret_cast<uintptr_t>(emb) % 16 == 0) &&
                       (!sum_e || reinterpret_cast<uintptr_t>(sum_e) % 16 == 0) &&
                       (!emb_out || reinterpret_cast<uintptr_t>(emb_out) % 16 == 0);
-#define CTR_FM_VEC(K4_, FMAX_)                                                              \
-  hipLaunchKernelGGL((fm_forward_vec<IdxT, K4_, FMAX_>), grid, block, 0, st, idx, B, F, V,  \
-                     reinterpret_cast<const float4*>(emb), lin, bias, z,                    \
-                     reinterpret_cast<float4*>(sum_e), reinterpret_cast<float4*>(emb_out),  \
-                     labels, mean_div, p, loss, gz, err,                                    \
-                     xpl ? static_cast<uint16_t*>(xpl->data) : nullptr, xpl ? xpl->ld : 0,  \
-                     xpl ? xpl->plane_stride : 0)
-  if (vec_ok) {
-    const int K4 = K / 4;
-    const bool f32 = F <= 32;
-    switch (K4) {
-      case 1: if (f32) CTR_FM_VEC(1, 32); else CTR_FM_VEC(1, 64); break;
-      case 2: if (f32) CTR_FM_VEC(2, 32); else CTR_FM_VEC(2, 64); break;
-      case 4: if (f32) CTR_FM_VEC(4, 32); else CTR_FM_VEC(4, 64); break;
-      case 8: if (f32) CTR_FM_VEC(8, 32); else CTR_FM_VEC(8, 64); break;
-      case 16: if (f32) CTR_FM_VEC(16, 32); else CTR_FM_VEC(16, 64); break;
-      case 32: if (f32) CTR_FM_VEC(32, 32); else CTR_FM_VEC(32, 64); break;
-      case 64: if (f32) CTR_FM_VEC(64, 32); else CTR_FM_VEC(64, 64); break;
-      default: goto generic;
-    }
-#undef CTR_FM_VEC
+  const bool f32 = F <= 32;
+  if (vec_ok && dispatch_width(K / 4, [&](auto k4) {
+        dispatch_bool(f32, [&](auto small) {
+          constexpr int FMAX = decltype(small)::value ? 32 : 64;
+          hipLaunchKernelGGL((fm_forward_vec<IdxT, decltype(k4)::value, FMAX>), grid, block, 0, st,
+                             idx, B, F, V, reinterpret_cast<const float4*>(emb), lin, bias, z,
+                             reinterpret_cast<float4*>(sum_e), reinterpret_cast<float4*>(emb_out),
+                             labels, mean_div, p, loss, gz, err,
+                             xpl ? static_cast<uint16_t*>(xpl->data) : nullptr,
+                             xpl ? xpl->ld : 0, xpl ? xpl->plane_stride : 0);
+        });
+      })) {
     CTR_LAUNCH_CHECK("fm_forward_vec");
     return CTR_OK;
   }
-generic:
   CTR_REQUIRE(!xpl, "ctr_fm_forward_planes: needs K %% 4 == 0, (K/4) | 64, F <= 64, 16-B rows");
   hipLaunchKernelGGL((fm_forward_generic<IdxT>), grid, block, 0, st, idx, B, F, K, V, emb, lin,
                      bias, z, sum_e, emb_out, labels, mean_div, p, loss, gz, err);

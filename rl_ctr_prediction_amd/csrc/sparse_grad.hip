@@ -436,27 +436,12 @@ static int launch_seg(SegArgs& a, int K, int mode, hipStream_t st, bool aligned1
   const int KV = vec ? K / 4 : K;
   a.KV = KV;
   const int lpr = pow2_at_least(KV);
-  if (vec) {
-    switch (lpr) {
-      case 1: return launch_seg_lpr<float4, 1>(a, mode, st);
-      case 2: return launch_seg_lpr<float4, 2>(a, mode, st);
-      case 4: return launch_seg_lpr<float4, 4>(a, mode, st);
-      case 8: return launch_seg_lpr<float4, 8>(a, mode, st);
-      case 16: return launch_seg_lpr<float4, 16>(a, mode, st);
-      case 32: return launch_seg_lpr<float4, 32>(a, mode, st);
-      case 64: return launch_seg_lpr<float4, 64>(a, mode, st);
-    }
-  } else {
-    switch (lpr) {
-      case 1: return launch_seg_lpr<float, 1>(a, mode, st);
-      case 2: return launch_seg_lpr<float, 2>(a, mode, st);
-      case 4: return launch_seg_lpr<float, 4>(a, mode, st);
-      case 8: return launch_seg_lpr<float, 8>(a, mode, st);
-      case 16: return launch_seg_lpr<float, 16>(a, mode, st);
-      case 32: return launch_seg_lpr<float, 32>(a, mode, st);
-      case 64: return launch_seg_lpr<float, 64>(a, mode, st);
-    }
-  }
+  int rc = CTR_OK;
+  if (dispatch_width(lpr, [&](auto n) {
+        constexpr int LPR = decltype(n)::value;
+        rc = vec ? launch_seg_lpr<float4, LPR>(a, mode, st) : launch_seg_lpr<float, LPR>(a, mode, st);
+      }))
+    return rc;
   set_error("segmented row sum: K=%d unsupported (K<=64, or K%%4==0 and K<=256)", K);
   return CTR_ERR_UNSUPPORTED;
 }

@@ -315,7 +315,7 @@ def _emb_check(msg, got, t, rows, gr, gl, step, wd):
     _check_ref(msg, got, t, last0, step - 1, wd, grads=gd, glin=gld)
 
 
-@pytest.mark.parametrize("K", [1, 3, 4, 8, 12, 16, 64, 128, 256, 260])
+@pytest.mark.parametrize("K", [1, 3, 4, 8, 12, 16, 32, 64, 128, 256, 260])
 def test_adam_embedding_shapes(cuda, tab, K):
     """Every K/4 instantiation and the thread-per-row kernel (K % 4 != 0, K/4 not a divisor
     of 64, K > 256), V below / at / above a 64-row tile and over several blocks; step 5 from
@@ -484,7 +484,7 @@ def _flush_all_ways(t, cuda, last0, step, tab, msg, ids_ok):
     return flush
 
 
-@pytest.mark.parametrize("K", [4, 8, 16, 40, 64, 256])
+@pytest.mark.parametrize("K", [4, 8, 16, 32, 40, 64, 128, 256])
 def test_adam_deferred_flush_shapes(cuda, tab, K):
     """last uniform in [0, T]: rows of every staleness in one tile, current rows among them;
     V below / at / above a tile; K = 40 (K/4 does not divide 64) takes the thread-per-row
@@ -605,7 +605,7 @@ def test_adam_deferred_catchup_ids_slot_loop(cuda, tab):
 
 
 # ================================================= 6. the fused scatter + Adam ===========
-@pytest.mark.parametrize("K", [4, 8, 128, 256])
+@pytest.mark.parametrize("K", [4, 8, 16, 32, 64, 128, 256])
 def test_fused_scatter_adam_direct(cuda, tab, K):
     """ctr_fm_embedding_grad_adam / ctr_segment_sum_rows_adam called directly: 600 slots over
     50 rows, one row owning a third of them (it spans many 16-position chunks and takes the

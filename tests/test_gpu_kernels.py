@@ -816,7 +816,8 @@ def test_shard_rows_lin_exchange_layout(cuda, n, C, K, lin):
         assert np.array_equal(backl.cpu().numpy()[:U], lv[:U])
 
 
-@pytest.mark.parametrize("K,lin", [(64, True), (16, True), (32, False)])
+@pytest.mark.parametrize("K,lin", [(64, True), (16, True), (32, False), (4, True), (8, False),
+                                   (128, True), (256, False)])
 def test_adam_deferred_entries_equals_sums_then_rows(cuda, K, lin):
     """ctr_adam_deferred_entries (the row-sharded owner: each row's entries summed straight,
     then replayed + stepped) == numpy's sequential fp32 sums in plan order, and the table after
