@@ -94,6 +94,16 @@ int ctr_fm_forward(const void* idx, int idx_type, int64_t B, int F, int K, int64
                    float* p, float* loss_elem, float* gz,
                    int32_t* err_flag, ctr_stream_t stream);
 
+/* LR forward: z[b] = bias[0] + sum_f lin[x_bf], the F weights added in field order
+ * (((w_0 + w_1) + w_2) + ...), and p = sigmoid(z); with labels the BCE head of ctr_fm_forward
+ * (p, loss_elem, gz). z, p, loss_elem and gz may be NULL individually. 1 <= F <= 64; a row is
+ * a group of lanes (several rows per wave when F < 64), never one thread. Out-of-range ids, null
+ * pointers and bad sizes as ctr_fm_forward.
+ * Replaces: p_model.py:18-26 (LR.forward), nn.BCELoss at all_main/pretrain_main.py:74. */
+int ctr_lr_forward(const void* idx, int idx_type, int64_t B, int F, int64_t V, const float* lin,
+                   const float* bias, float* z, float* p, const float* labels, float mean_div,
+                   float* loss_elem, float* gz, int32_t* err_flag, ctr_stream_t stream);
+
 /* BCE after sigmoid on precomputed logits (same formulas as the fused FM head).
  * Replaces: torch.sigmoid (p_model.py:55,324) + nn.BCELoss (pretrain_main.py:74). */
 int ctr_bce_sigmoid(const float* z, const float* labels, int64_t B, float mean_div,
@@ -587,6 +597,18 @@ int ctr_ensemble_preds(const float* preds, int64_t B, int M, int64_t ld_preds,
                        const float* c_actions, const void* labels, int label_type,
                        float* y_preds, float* rewards, float* return_c_actions, int32_t* rank_ws,
                        ctr_stream_t stream);
+/* ctr_ensemble_preds_ex: the same with flags; ctr_ensemble_preds is this with flags = 0.
+ *   CTR_ENSEMBLE_TIE_REWARDS: the reward compares with >= (label 1) and <= (label 0), so a tie
+ *   with the models' mean earns 1: the base driver's rule (hybrid_td3_main_per.py:114-126).
+ *   c_actions NULL: prob_weights take their place (the base driver's generate_preds, lines
+ *   56-133, has no c_actions: its softmax runs over the largest prob_weights).
+ *   return_c_actions NULL: not computed; rank_ws may then be NULL too. */
+enum ctr_ensemble_flags { CTR_ENSEMBLE_TIE_REWARDS = 1 };
+int ctr_ensemble_preds_ex(const float* preds, int64_t B, int M, int64_t ld_preds,
+                          const void* actions, int action_type, const float* prob_weights,
+                          const float* c_actions, const void* labels, int label_type,
+                          float* y_preds, float* rewards, float* return_c_actions,
+                          int32_t* rank_ws, int flags, ctr_stream_t stream);
 
 /* ------------------------------------------------ §8f: FFM (field-aware FM) ---------
  * tables: a DEVICE array of F pointers, table t = field t's embedding [V, K] (K <= 64,
@@ -697,6 +719,19 @@ int64_t ctr_per_workspace_bytes(int64_t N, int k);
 int ctr_per_add(int64_t N, int T, int64_t start, int64_t n, const float* transitions,
                 int64_t ldt, const float* td, float eps, float alpha, float* memory,
                 float* prio, ctr_stream_t stream);
+/* ctr_per_store_step: the driver's per-batch store in one launch (the two .float() casts, the
+ *   cat of five tensors, the ones and ctr_per_add). Row i < n goes to slot (start + i) % N:
+ *   memory[slot] = [ (float)idx[i, 0..F) | c_actions[i, 0..A) | d_values[i, 0..A) |
+ *   (float)d_action[i] | rewards[i] ], T == F + 2A + 2, and prio[slot] = max(prio[slot],
+ *   priority(1.0f)), the expression ctr_per_add evaluates (the same bits). The conversions
+ *   round to nearest even (torch's cast). idx [n, F] and d_action [n] are contiguous int32 or
+ *   int64; c_actions, d_values and rewards have row strides ldc, ldd (>= A) and ldr (>= 1).
+ *   Plain stores, no atomics. n == 0 is a no-op; n > N is refused. */
+int ctr_per_store_step(int64_t N, int T, int64_t start, int64_t n, int F, int A, const void* idx,
+                       int idx_type, const float* c_actions, int64_t ldc, const float* d_values,
+                       int64_t ldd, const void* d_action, int action_type, const float* rewards,
+                       int64_t ldr, float eps, float alpha, float* memory, float* prio,
+                       ctr_stream_t stream);
 int ctr_per_update(int64_t N, int64_t k, const int64_t* idx, const float* td, float eps,
                    float alpha, float* prio, ctr_stream_t stream);
 int ctr_per_keys(int64_t n_valid, const float* prio, int mode, uint64_t seed, float* keys,

@@ -19,6 +19,7 @@ CTR_EFLAG_CAPACITY = 2
 CTR_LABEL_F32, CTR_LABEL_I32, CTR_LABEL_I64 = 0, 1, 2
 CTR_METRICS_FLAG_NAN, CTR_METRICS_FLAG_LABEL, CTR_METRICS_FLAG_RANGE = 1, 2, 4
 CTR_METRICS_STATE_BYTES = 128
+CTR_ENSEMBLE_TIE_REWARDS = 1
 EPI_NONE, EPI_BIAS, EPI_BIAS_RELU, EPI_BIAS_RELU_DROP, EPI_GRAD_MASK = range(5)
 
 _vp, _i32, _i64, _f32, _f64, _u64 = C.c_void_p, C.c_int, C.c_int64, C.c_float, C.c_double, C.c_uint64
@@ -181,6 +182,8 @@ SIGNATURES = {
     "ctr_embedding_gather": (_i32, [_vp, _i64, _i32, _vp, _i32, _i64, _vp, _vp, _vp]),
     "ctr_fm_forward": (_i32, [_vp, _i32, _i64, _i32, _i32, _i64, _vp, _vp, _vp, _vp, _vp, _vp,
                               _vp, _f32, _vp, _vp, _vp, _vp, _vp]),
+    "ctr_lr_forward": (_i32, [_vp, _i32, _i64, _i32, _i64, _vp, _vp, _vp, _vp, _vp, _f32, _vp, _vp,
+                              _vp, _vp]),
     "ctr_bce_sigmoid": (_i32, [_vp, _vp, _i64, _f32, _vp, _vp, _vp, _vp]),
     "ctr_deepfm_head": (_i32, [_vp, _i64, _i32, _vp, _vp, _vp, _vp, _f32, _f32, _vp, _vp, _vp,
                                _vp, _vp, _vp]),
@@ -269,6 +272,8 @@ SIGNATURES = {
                                                     _vp, _planes_p, _vp, _vp]),
     "ctr_ensemble_preds": (_i32, [_vp, _i64, _i32, _i64, _vp, _i32, _vp, _vp, _vp, _i32, _vp, _vp,
                                   _vp, _vp, _vp]),
+    "ctr_ensemble_preds_ex": (_i32, [_vp, _i64, _i32, _i64, _vp, _i32, _vp, _vp, _vp, _i32, _vp,
+                                     _vp, _vp, _vp, _i32, _vp]),
     "ctr_ffm_forward": (_i32, [_vp, _i32, _i64, _i32, _i32, _i64, _vp, _vp, _vp, _vp, _vp, _f32,
                                _vp, _vp, _vp, _vp, _vp]),
     "ctr_ffm_keys": (_i32, [_vp, _i32, _i64, _i32, _i64, _vp, _vp, _vp]),
@@ -286,6 +291,8 @@ SIGNATURES = {
                                       _vp, _vp, _i64, _vp, _vp, _vp, _vp, _i64, _vp]),
     "ctr_per_workspace_bytes": (_i64, [_i64, _i32]),
     "ctr_per_add": (_i32, [_i64, _i32, _i64, _i64, _vp, _i64, _vp, _f32, _f32, _vp, _vp, _vp]),
+    "ctr_per_store_step": (_i32, [_i64, _i32, _i64, _i64, _i32, _i32, _vp, _i32, _vp, _i64, _vp,
+                                  _i64, _vp, _i32, _vp, _i64, _f32, _f32, _vp, _vp, _vp]),
     "ctr_per_update": (_i32, [_i64, _i64, _vp, _vp, _f32, _f32, _vp, _vp]),
     "ctr_per_keys": (_i32, [_i64, _vp, _i32, _u64, _vp, _vp]),
     "ctr_per_sample": (_i32, [_i64, _i32, _i64, _i32, _i32, _u64, _f32, _vp, _vp, _vp, _vp, _vp,

@@ -17,6 +17,12 @@
 //   reward:  label 1: y > mean_m preds[b,m] ? 1 : 0; label 0: y < mean ? 1 : 0 (137-157)
 //   actions outside 1..M: y = 1, reward = 1, ret_c = 0 (the tensors' initial values)
 //
+// ctr_ensemble_preds_ex also serves the base driver's function (hybrid_td3_main_per.py:56-133),
+// which has no c_actions: its softmax runs over the a largest pw themselves (its i == 1 branch
+// is that softmax over one element, exactly 1), which is the above with ca := pw (c_actions
+// NULL), and it rewards a tie with the mean (>= / <=: CTR_ENSEMBLE_TIE_REWARDS). Without
+// return_c_actions neither ret_c nor the ordinals are computed.
+//
 // The per-action ordinals come from one 1024-thread block walking the batch in order with
 // wave ballots (stable by construction); the rest is one thread per example with M <= 32
 // values in registers (top-a by repeated arg-max: a <= M <= 32, no sort needed).
@@ -68,7 +74,7 @@ template <typename AT, typename LT>
 __global__ __launch_bounds__(256) void ensemble_preds_kernel(
     const float* __restrict__ preds, int64_t ldp, const AT* __restrict__ act,
     const float* __restrict__ pw, const float* __restrict__ ca, const LT* __restrict__ labels,
-    const int32_t* __restrict__ rank, int64_t B, int M, float* __restrict__ y_out,
+    const int32_t* __restrict__ rank, int64_t B, int M, bool tie, float* __restrict__ y_out,
     float* __restrict__ r_out, float* __restrict__ rc_out) {
 #pragma clang fp contract(off)  // the reference's separate torch.mul / torch.sum roundings
   for (int64_t b = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; b < B;
@@ -97,7 +103,8 @@ __global__ __launch_bounds__(256) void ensemble_preds_kernel(
             rc[m] = cab[m];
           }
       } else {
-        const float* caj = ca + (int64_t)rank[b] * M;  // the reference's local-index row
+        // the reference's local-index row (feeds rc alone: not read without rc_out)
+        const float* caj = rc_out ? ca + (int64_t)rank[b] * M : cab;
         uint32_t used_p = 0, used_c = 0, used_j = 0;
         float top_c[kMaxModels], row_p[kMaxModels];
         for (int m = 0; m < a; ++m) {
@@ -128,28 +135,30 @@ __global__ __launch_bounds__(256) void ensemble_preds_kernel(
         for (int m = 0; m < a; ++m) y += (e[m] / den) * row_p[m];
       }
       const int64_t lab = (int64_t)labels[b];
-      if (lab == 1) reward = y > mean ? 1.f : 0.f;
-      else if (lab == 0) reward = y < mean ? 1.f : 0.f;
+      if (lab == 1) reward = (tie ? y >= mean : y > mean) ? 1.f : 0.f;
+      else if (lab == 0) reward = (tie ? y <= mean : y < mean) ? 1.f : 0.f;
     }
     y_out[b] = y;
     r_out[b] = reward;
 #pragma unroll
     for (int m = 0; m < kMaxModels; ++m)
-      if (m < M) rc_out[b * M + m] = rc[m];
+      if (rc_out && m < M) rc_out[b * M + m] = rc[m];
   }
 }
 
 template <typename AT, typename LT>
 static int launch_ensemble(const float* preds, int64_t ldp, const void* act, const float* pw,
                            const float* ca, const void* labels, int32_t* rank, int64_t B, int M,
-                           float* y, float* r, float* rc, hipStream_t st) {
-  hipLaunchKernelGGL(action_rank_kernel<AT>, 1, 1024, 0, st, static_cast<const AT*>(act), B, M,
-                     rank);
-  CTR_LAUNCH_CHECK("action_rank_kernel");
+                           bool tie, float* y, float* r, float* rc, hipStream_t st) {
+  if (rc) {  // the ordinals index the returned c_actions only
+    hipLaunchKernelGGL(action_rank_kernel<AT>, 1, 1024, 0, st, static_cast<const AT*>(act), B, M,
+                       rank);
+    CTR_LAUNCH_CHECK("action_rank_kernel");
+  }
   const unsigned grid = (unsigned)std::min<int64_t>(ceil_div(B, 256), 4096);
   hipLaunchKernelGGL((ensemble_preds_kernel<AT, LT>), grid, 256, 0, st, preds, ldp,
                      static_cast<const AT*>(act), pw, ca, static_cast<const LT*>(labels), rank,
-                     B, M, y, r, rc);
+                     B, M, tie, y, r, rc);
   CTR_LAUNCH_CHECK("ensemble_preds_kernel");
   return CTR_OK;
 }
@@ -158,36 +167,62 @@ static int launch_ensemble(const float* preds, int64_t ldp, const void* act, con
 
 using namespace ctr;
 
-extern "C" int ctr_ensemble_preds(const float* preds, int64_t B, int M, int64_t ld_preds,
-                                  const void* actions, int action_type, const float* prob_weights,
-                                  const float* c_actions, const void* labels, int label_type,
-                                  float* y_preds, float* rewards, float* return_c_actions,
-                                  int32_t* rank_ws, ctr_stream_t stream) {
+// v10: the old entry point, whose c_actions and return_c_actions are not optional
+static int ensemble_entry(const float* preds, int64_t B, int M, int64_t ld_preds,
+                          const void* actions, int action_type, const float* prob_weights,
+                          const float* c_actions, const void* labels, int label_type,
+                          float* y_preds, float* rewards, float* return_c_actions,
+                          int32_t* rank_ws, int flags, bool v10, ctr_stream_t stream) {
   CTR_REQUIRE(B >= 0 && M >= 1 && M <= kMaxModels && ld_preds >= M,
               "ctr_ensemble_preds: need 1 <= M <= %d models and ld_preds >= M", kMaxModels);
   CTR_REQUIRE(action_type == CTR_IDX_I32 || action_type == CTR_IDX_I64, "bad action_type %d",
               action_type);
   CTR_REQUIRE(label_type == CTR_IDX_I32 || label_type == CTR_IDX_I64, "bad label_type %d",
               label_type);
+  CTR_REQUIRE((flags & ~CTR_ENSEMBLE_TIE_REWARDS) == 0, "ctr_ensemble_preds: unknown flags %d",
+              flags);
   if (B == 0) return CTR_OK;
-  CTR_REQUIRE(preds && actions && prob_weights && c_actions && labels && y_preds && rewards &&
-                  return_c_actions && rank_ws,
+  CTR_REQUIRE(preds && actions && prob_weights && labels && y_preds && rewards &&
+                  (!return_c_actions || rank_ws) && (!v10 || (c_actions && return_c_actions)),
               "ctr_ensemble_preds: null pointer");
+  if (!c_actions) c_actions = prob_weights;  // the base driver: softmax of the weights themselves
+  const bool tie = (flags & CTR_ENSEMBLE_TIE_REWARDS) != 0;
   hipStream_t st = as_stream(stream);
   const bool a64 = action_type == CTR_IDX_I64, l64 = label_type == CTR_IDX_I64;
   if (a64 && l64)
     return launch_ensemble<int64_t, int64_t>(preds, ld_preds, actions, prob_weights, c_actions,
-                                             labels, rank_ws, B, M, y_preds, rewards,
+                                             labels, rank_ws, B, M, tie, y_preds, rewards,
                                              return_c_actions, st);
   if (a64)
     return launch_ensemble<int64_t, int32_t>(preds, ld_preds, actions, prob_weights, c_actions,
-                                             labels, rank_ws, B, M, y_preds, rewards,
+                                             labels, rank_ws, B, M, tie, y_preds, rewards,
                                              return_c_actions, st);
   if (l64)
     return launch_ensemble<int32_t, int64_t>(preds, ld_preds, actions, prob_weights, c_actions,
-                                             labels, rank_ws, B, M, y_preds, rewards,
+                                             labels, rank_ws, B, M, tie, y_preds, rewards,
                                              return_c_actions, st);
   return launch_ensemble<int32_t, int32_t>(preds, ld_preds, actions, prob_weights, c_actions,
-                                           labels, rank_ws, B, M, y_preds, rewards,
+                                           labels, rank_ws, B, M, tie, y_preds, rewards,
                                            return_c_actions, st);
+}
+
+extern "C" int ctr_ensemble_preds_ex(const float* preds, int64_t B, int M, int64_t ld_preds,
+                                     const void* actions, int action_type,
+                                     const float* prob_weights, const float* c_actions,
+                                     const void* labels, int label_type, float* y_preds,
+                                     float* rewards, float* return_c_actions, int32_t* rank_ws,
+                                     int flags, ctr_stream_t stream) {
+  return ensemble_entry(preds, B, M, ld_preds, actions, action_type, prob_weights, c_actions,
+                        labels, label_type, y_preds, rewards, return_c_actions, rank_ws, flags,
+                        false, stream);
+}
+
+extern "C" int ctr_ensemble_preds(const float* preds, int64_t B, int M, int64_t ld_preds,
+                                  const void* actions, int action_type, const float* prob_weights,
+                                  const float* c_actions, const void* labels, int label_type,
+                                  float* y_preds, float* rewards, float* return_c_actions,
+                                  int32_t* rank_ws, ctr_stream_t stream) {
+  return ensemble_entry(preds, B, M, ld_preds, actions, action_type, prob_weights, c_actions,
+                        labels, label_type, y_preds, rewards, return_c_actions, rank_ws, 0, true,
+                        stream);
 }

@@ -173,6 +173,48 @@ __global__ __launch_bounds__(256) void fm_forward_generic(
   }
 }
 
+// ------------------------------------------------------------------ LR forward ------
+// z = bias + sum_f lin[x_f] (p_model.py:18-26). A row is G = the power of two >= F lanes, a wave
+// holds 64 / G rows: every lane gathers one weight (all of a wave's gathers in flight at once),
+// then each row's lanes add the F weights in field order (G broadcasts inside the row's lane
+// group), so z is the same bits for a row wherever it sits in the batch.
+template <typename IdxT, int G>
+__global__ __launch_bounds__(256) void lr_forward_kernel(
+    const IdxT* __restrict__ idx, int64_t B, int F, int64_t V, const float* __restrict__ lin,
+    const float* __restrict__ bias, float* __restrict__ z_out, float* __restrict__ p_out,
+    const float* __restrict__ labels, float mean_div, float* __restrict__ loss_out,
+    float* __restrict__ gz_out, int32_t* err) {
+  constexpr int RPW = kWave / G;  // rows of a wave
+  const int lane = threadIdx.x & (kWave - 1);
+  const int64_t wave = (int64_t)blockIdx.x * (blockDim.x / kWave) + (threadIdx.x / kWave);
+  if (wave * RPW >= B) return;  // wave-uniform
+  const int f = lane % G, base = lane - f;
+  const int64_t b = wave * RPW + lane / G;
+  const bool row = b < B;
+  const float yb = (labels && row) ? labels[b] : 0.f;  // in flight with the gather
+  float w = 0.f;
+  if (row && f < F) w = lin[load_row(idx, b * F + f, V, err)];
+  float acc = 0.f;
+#pragma unroll
+  for (int j = 0; j < G; ++j) {  // every lane takes part in the broadcast
+    const float v = __shfl(w, base + j, kWave);
+    if (j < F) acc = j == 0 ? v : acc + v;
+  }
+  if (row && f == 0) {
+    const float z = bias[0] + acc;  // p_model.py:23
+    if (z_out) z_out[b] = z;
+    if (labels) {
+      float p, l, g;
+      bce_sigmoid_head(z, yb, mean_div, p, l, g);
+      if (p_out) p_out[b] = p;
+      if (loss_out) loss_out[b] = l;
+      if (gz_out) gz_out[b] = g;
+    } else if (p_out) {
+      p_out[b] = sigmoidf_ref(z);
+    }
+  }
+}
+
 // ------------------------------------------------------------------ BCE head -------
 __global__ __launch_bounds__(256) void bce_sigmoid_kernel(const float* __restrict__ z,
                                                           const float* __restrict__ y, int64_t B,
@@ -349,9 +391,44 @@ static int launch_fm_forward(const IdxT* idx, int64_t B, int F, int K, int64_t V
   return CTR_OK;
 }
 
+template <typename IdxT>
+static int launch_lr_forward(const IdxT* idx, int64_t B, int F, int64_t V, const float* lin,
+                             const float* bias, float* z, float* p, const float* labels,
+                             float mean_div, float* loss, float* gz, int32_t* err,
+                             hipStream_t st) {
+  int G = 1;
+  while (G < F) G <<= 1;
+  const int64_t waves = ceil_div(B, kWave / G);
+  dispatch_width(G, [&](auto g) {  // F <= 64: G is one of the widths
+    hipLaunchKernelGGL((lr_forward_kernel<IdxT, decltype(g)::value>), (unsigned)ceil_div(waves, 4),
+                       256, 0, st, idx, B, F, V, lin, bias, z, p, labels, mean_div, loss, gz, err);
+  });
+  CTR_LAUNCH_CHECK("lr_forward_kernel");
+  return CTR_OK;
+}
+
 }  // namespace ctr
 
 using namespace ctr;
+
+extern "C" int ctr_lr_forward(const void* idx, int idx_type, int64_t B, int F, int64_t V,
+                              const float* lin, const float* bias, float* z, float* p,
+                              const float* labels, float mean_div, float* loss_elem, float* gz,
+                              int32_t* err_flag, ctr_stream_t stream) {
+  CTR_REQUIRE(idx && lin && bias, "ctr_lr_forward: null input pointer");
+  CTR_REQUIRE(B >= 0 && F > 0 && F <= 64 && V > 0 && V < (int64_t(1) << 31),
+              "ctr_lr_forward: bad sizes B=%lld F=%d (1..64) V=%lld", (long long)B, F,
+              (long long)V);
+  CTR_REQUIRE(idx_type == CTR_IDX_I32 || idx_type == CTR_IDX_I64, "bad idx_type %d", idx_type);
+  CTR_REQUIRE(!labels || mean_div > 0.f, "ctr_lr_forward: mean_div must be > 0");
+  if (B == 0) return CTR_OK;
+  hipStream_t st = as_stream(stream);
+  if (idx_type == CTR_IDX_I64)
+    return launch_lr_forward(static_cast<const int64_t*>(idx), B, F, V, lin, bias, z, p, labels,
+                             mean_div, loss_elem, gz, err_flag, st);
+  return launch_lr_forward(static_cast<const int32_t*>(idx), B, F, V, lin, bias, z, p, labels,
+                           mean_div, loss_elem, gz, err_flag, st);
+}
 
 extern "C" int ctr_embedding_gather(const float* table, int64_t V, int K, const void* idx,
                                     int idx_type, int64_t n, float* out, int32_t* err_flag,

@@ -171,6 +171,35 @@ __global__ __launch_bounds__(kPerThreads) void per_add_kernel(
   }
 }
 
+// The driver's per-batch store in one launch: the transition row is packed from its five
+// sources straight into its slot ([ids | c_actions | d_values | d_action | reward], the ids and
+// the action as floats: round-to-nearest-even, what torch's .float() gives) and the slot takes
+// the priority of a fresh transition (td = 1). Plain stores: n <= N, every slot has one writer.
+template <typename IdxT, typename ActT>
+__global__ __launch_bounds__(kPerThreads) void per_store_step_kernel(
+    int64_t N, int T, int64_t start, int64_t n, int F, int A, const IdxT* __restrict__ idx,
+    const float* __restrict__ c_actions, int64_t ldc, const float* __restrict__ d_values,
+    int64_t ldd, const ActT* __restrict__ d_action, const float* __restrict__ rewards,
+    int64_t ldr, float eps, float alpha, float* __restrict__ memory, float* __restrict__ prio) {
+  const int64_t total = n * T, step = (int64_t)gridDim.x * kPerThreads;
+  for (int64_t it = (int64_t)blockIdx.x * kPerThreads + threadIdx.x; it < total; it += step) {
+    const int64_t i = it / T;
+    const int c = (int)(it - i * T);
+    const int64_t row = (start + i) % N;
+    float v;
+    if (c < F) v = (float)idx[i * F + c];
+    else if (c < F + A) v = c_actions[i * ldc + (c - F)];
+    else if (c < F + 2 * A) v = d_values[i * ldd + (c - F - A)];
+    else if (c == F + 2 * A) v = (float)d_action[i];
+    else v = rewards[i * ldr];  // c == T - 1 (T == F + 2A + 2, checked on the host)
+    memory[row * T + c] = v;
+    if (c == 0) {
+      const float pn = per_priority(1.0f, eps, alpha), old = prio[row];
+      prio[row] = (pn > old || pn != pn) ? pn : old;  // as per_add_kernel
+    }
+  }
+}
+
 __global__ __launch_bounds__(kPerThreads) void per_update_kernel(
     int64_t N, int64_t k, const int64_t* __restrict__ idx, const float* __restrict__ td,
     float eps, float alpha, float* __restrict__ prio) {
@@ -495,6 +524,47 @@ extern "C" int ctr_per_add(int64_t N, int T, int64_t start, int64_t n, const flo
                        n, transitions, ldt, td, eps, alpha, memory, prio);
   }
   CTR_LAUNCH_CHECK("ctr_per_add");
+  return CTR_OK;
+}
+
+extern "C" int ctr_per_store_step(int64_t N, int T, int64_t start, int64_t n, int F, int A,
+                                  const void* idx, int idx_type, const float* c_actions,
+                                  int64_t ldc, const float* d_values, int64_t ldd,
+                                  const void* d_action, int action_type, const float* rewards,
+                                  int64_t ldr, float eps, float alpha, float* memory, float* prio,
+                                  ctr_stream_t stream) {
+  int rc = per_check_sizes("ctr_per_store_step", N, T);
+  if (rc != CTR_OK) return rc;
+  CTR_REQUIRE(F >= 1 && A >= 1 && (int64_t)F + 2 * (int64_t)A + 2 == T,
+              "ctr_per_store_step: T=%d is not F + 2A + 2 (F=%d, A=%d)", T, F, A);
+  CTR_REQUIRE(n >= 0 && n <= N, "ctr_per_store_step: n=%lld outside [0, N=%lld]", (long long)n,
+              (long long)N);
+  CTR_REQUIRE(start >= 0 && start < N, "ctr_per_store_step: start=%lld outside [0, N=%lld)",
+              (long long)start, (long long)N);
+  CTR_REQUIRE(idx_type == CTR_IDX_I32 || idx_type == CTR_IDX_I64, "bad idx_type %d", idx_type);
+  CTR_REQUIRE(action_type == CTR_IDX_I32 || action_type == CTR_IDX_I64, "bad action_type %d",
+              action_type);
+  CTR_REQUIRE(memory && prio, "ctr_per_store_step: null memory / prio");
+  if (n == 0) return CTR_OK;
+  CTR_REQUIRE(idx && c_actions && d_values && d_action && rewards,
+              "ctr_per_store_step: null idx / c_actions / d_values / d_action / rewards");
+  CTR_REQUIRE(ldc >= A && ldd >= A && ldr >= 1,
+              "ctr_per_store_step: row strides ldc=%lld ldd=%lld (>= A) ldr=%lld (>= 1)",
+              (long long)ldc, (long long)ldd, (long long)ldr);
+  hipStream_t st = as_stream(stream);
+  const unsigned grid = per_grid(n * T);
+  const bool i64 = idx_type == CTR_IDX_I64, a64 = action_type == CTR_IDX_I64;
+  dispatch_bool(i64, [&](auto wi) {
+    dispatch_bool(a64, [&](auto wa) {
+      using IdxT = std::conditional_t<decltype(wi)::value, int64_t, int32_t>;
+      using ActT = std::conditional_t<decltype(wa)::value, int64_t, int32_t>;
+      hipLaunchKernelGGL((per_store_step_kernel<IdxT, ActT>), grid, kPerThreads, 0, st, N, T,
+                         start, n, F, A, static_cast<const IdxT*>(idx), c_actions, ldc, d_values,
+                         ldd, static_cast<const ActT*>(d_action), rewards, ldr, eps, alpha, memory,
+                         prio);
+    });
+  });
+  CTR_LAUNCH_CHECK("ctr_per_store_step");
   return CTR_OK;
 }
 

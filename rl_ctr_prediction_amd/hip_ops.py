@@ -14,7 +14,7 @@ from dataclasses import dataclass
 
 import torch
 
-from ._lib import (CTR_EFLAG_CAPACITY, CTR_EFLAG_INDEX, CTR_IDX_I32, CTR_IDX_I64, CTR_LABEL_F32,
+from ._lib import (CTR_EFLAG_CAPACITY, CTR_EFLAG_INDEX, CTR_ENSEMBLE_TIE_REWARDS, CTR_IDX_I32, CTR_IDX_I64, CTR_LABEL_F32,
                    CTR_LABEL_I32, CTR_LABEL_I64, EPI_BIAS, EPI_BIAS_RELU,
                    EPI_BIAS_RELU_DROP, EPI_GRAD_MASK, EPI_NONE, PlanesDesc, PlaneViewDesc, SparsePlan,
                    CtrHipError, lib)
@@ -25,6 +25,7 @@ __all__ = [
     "fm_embedding_grad_adam", "segment_sum_rows_adam",
     "rows_to_dense", "adam_dense", "fm_step_tail", "adam_embedding", "adam_scalars", "feature_embedding",
     "dcn_cross_forward", "dcn_cross_backward",
+    "lr_forward", "ensemble_preds", "ensemble_preds_ex", "per_store_step",
     "per_add", "per_update", "per_keys", "per_sample", "PER_STOCHASTIC", "PER_GREEDY", "PER_MAX_K",
     "metrics_workspace_bytes", "metrics_reset", "metrics_append", "metrics_auc", "METRICS_TILE",
     "METRICS_STATE_WORDS",
@@ -234,6 +235,36 @@ def fm_forward(idx: torch.Tensor, emb: torch.Tensor, lin: torch.Tensor, bias: to
     lib.ctr_fm_forward(_p(idx), it, B, F, K, V, _p(emb), _p(lin), _p(bias), _p(out.z),
                        _p(out.sum_e), _p(out.emb_out), _p(labels), float(mean_div or 1.0),
                        _p(out.p), _p(out.loss_elem), _p(out.gz), _p(err_flag), _stream())
+    return out
+
+
+def lr_forward(idx: torch.Tensor, lin: torch.Tensor, bias: torch.Tensor, *,
+               labels: torch.Tensor | None = None, mean_div: float | None = None,
+               want_p: bool = True, err_flag=None) -> dict:
+    """LR (p_model.py:18-26): z = bias + sum_f lin[x_f] in field order and p = sigmoid(z), with
+    the BCE head (loss_elem, gz) when labels are given: dict(z, p, loss_elem, gz), one launch."""
+    idx, it = _idx(idx)
+    if idx.dim() != 2:
+        raise ValueError("lr_forward: idx must be [B, F]")
+    B, F = idx.shape
+    if not 1 <= F <= 64:
+        raise ValueError(f"lr_forward: F={F} outside [1, 64]")
+    _f32(lin, "linear.weight")
+    _f32(bias, "bias")
+    if lin.dim() != 2 or lin.shape[1] != 1 or bias.numel() != 1:
+        raise ValueError("lr_forward: linear.weight must be [V, 1] and bias [1]")
+    V, dev = lin.shape[0], lin.device
+    e = lambda: torch.empty(B, dtype=torch.float32, device=dev)  # noqa: E731
+    out = dict(z=e(), p=e() if want_p else None, loss_elem=None, gz=None)
+    if labels is not None:
+        _f32(labels, "labels")
+        if labels.numel() != B:
+            raise ValueError(f"lr_forward: labels must hold {B} values")
+        mean_div = float(B if mean_div is None else mean_div)
+        out["loss_elem"], out["gz"] = e(), e()
+    lib.ctr_lr_forward(_p(idx), it, B, F, V, _p(lin), _p(bias), _p(out["z"]), _p(out["p"]),
+                       _p(labels), float(mean_div or 1.0), _p(out["loss_elem"]), _p(out["gz"]),
+                       _p(err_flag), _stream())
     return out
 
 
@@ -1377,6 +1408,48 @@ def per_add(memory: torch.Tensor, prio: torch.Tensor, start: int, transitions: t
                     eps, alpha, _p(memory), _p(prio), _stream())
 
 
+def _per_rows(t: torch.Tensor, name: str, n: int, D: int) -> int:
+    """float32 [n, D] with unit column stride (a view of a wider matrix is fine): its row
+    stride."""
+    _dev(t, name)
+    if t.dtype != torch.float32 or t.dim() != 2 or tuple(t.shape) != (n, D):
+        raise ValueError(f"per_store_step: {name} must be float32 [{n}, {D}]")
+    if n == 0:
+        return D
+    if D > 1 and t.stride(1) != 1:
+        raise ValueError(f"per_store_step: {name} must have unit column stride")
+    if n > 1 and t.stride(0) < D:
+        raise ValueError(f"per_store_step: {name} has row stride {t.stride(0)} < {D}")
+    return t.stride(0) if n > 1 else D
+
+
+def per_store_step(memory: torch.Tensor, prio: torch.Tensor, start: int, features: torch.Tensor,
+                   c_actions: torch.Tensor, d_values: torch.Tensor, d_actions: torch.Tensor,
+                   rewards: torch.Tensor, eps: float, alpha: float) -> None:
+    """The driver's per-batch store as one launch: memory[(start + i) % N] = [float(features[i])
+    | c_actions[i] | d_values[i] | float(d_actions[i]) | rewards[i]] and prio = max(prio,
+    (1 + eps)^alpha) there — bitwise what the casts, torch.cat and per_add(ones) leave."""
+    N, T = _per_store(memory, prio)
+    feats, it = _idx(features, "features")
+    if feats.dim() != 2:
+        raise ValueError("per_store_step: features must be [n, F]")
+    n, F = feats.shape
+    A = c_actions.shape[1] if isinstance(c_actions, torch.Tensor) and c_actions.dim() == 2 else -1
+    if A < 1 or T != F + 2 * A + 2:
+        raise ValueError(f"per_store_step: T={T} is not F + 2A + 2 (F={F}, A={A})")
+    if n > N:
+        raise ValueError(f"per_store_step: {n} transitions do not fit a memory of {N}")
+    ldc = _per_rows(c_actions, "c_actions", n, A)
+    ldd = _per_rows(d_values, "d_values", n, A)
+    ldr = _per_rows(rewards.view(n, 1) if rewards.dim() == 1 else rewards, "rewards", n, 1)
+    if d_actions.numel() != n:
+        raise ValueError(f"per_store_step: d_actions must hold {n} actions")
+    act, at = _idx(d_actions.reshape(n), "d_actions")
+    lib.ctr_per_store_step(N, T, start, n, F, A, _p(feats), it, _p(c_actions), ldc, _p(d_values),
+                           ldd, _p(act), at, _p(rewards), ldr, eps, alpha, _p(memory), _p(prio),
+                           _stream())
+
+
 def per_update(prio: torch.Tensor, idx: torch.Tensor, td: torch.Tensor, eps: float,
                alpha: float) -> None:
     """Memory.batch_update: prio[idx] = (|td| + eps)^alpha (duplicate indices: undefined)."""
@@ -1754,6 +1827,36 @@ def ensemble_preds(preds: torch.Tensor, actions: torch.Tensor, prob_weights: tor
     rank = torch.empty(max(B, 1), dtype=torch.int32, device=dev)
     lib.ctr_ensemble_preds(_p(preds), B, M, preds.stride(0), _p(act), at, _p(pw), _p(ca),
                            _p(lab), lt, _p(y), _p(r), _p(rc), _p(rank), _stream())
+    return y, r, rc
+
+
+def ensemble_preds_ex(preds: torch.Tensor, actions: torch.Tensor, prob_weights: torch.Tensor,
+                      labels: torch.Tensor, c_actions: torch.Tensor | None = None, *,
+                      tie_rewards: bool = False, want_c_actions: bool = True):
+    """ctr_ensemble_preds_ex: ensemble_preds with the base driver's options. c_actions=None:
+    the softmax weights come from prob_weights (hybrid_td3_main_per.py:56-133); tie_rewards:
+    a tie with the models' mean earns 1 (>= / <=). Returns (y_preds [B,1], rewards [B,1],
+    return_c_actions [B,M] or None)."""
+    _f32(preds, "preds")
+    if preds.dim() != 2:
+        raise ValueError("ensemble_preds_ex: preds must be [B, M]")
+    B, M = preds.shape
+    if not 1 <= M <= 32:
+        raise ValueError(f"ensemble_preds_ex: M={M} models outside [1, 32]")
+    pw = _f32(prob_weights.reshape(B, M).contiguous(), "prob_weights")
+    ca = None if c_actions is None else _f32(c_actions.reshape(B, M).contiguous(), "c_actions")
+    act, at = _idx(actions.reshape(B), "actions")
+    lab, lt = _idx(labels.reshape(B), "labels")
+    dev = preds.device
+    y = torch.empty(B, 1, dtype=torch.float32, device=dev)
+    r = torch.empty(B, 1, dtype=torch.float32, device=dev)
+    rc = rank = None
+    if want_c_actions:
+        rc = torch.empty(B, M, dtype=torch.float32, device=dev)
+        rank = torch.empty(max(B, 1), dtype=torch.int32, device=dev)
+    lib.ctr_ensemble_preds_ex(_p(preds), B, M, M, _p(act), at, _p(pw),
+                              _p(ca), _p(lab), lt, _p(y), _p(r), _p(rc), _p(rank),
+                              CTR_ENSEMBLE_TIE_REWARDS if tie_rewards else 0, _stream())
     return y, r, rc
 
 

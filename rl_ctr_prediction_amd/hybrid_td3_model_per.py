@@ -24,7 +24,8 @@ The actor loss's gradients for the critic's parameters, which the reference comp
 zeroes before they are used, are not computed.
 
 Extensions (keyword only, the defaults are the reference's behaviour): ``learn(sample=,
-noise=, return_tensor=)`` and ``choose_action(noise=)``. Generated noise is a stateless hash of
+noise=, return_tensor=)``, ``choose_action(noise=)`` and ``store_step(features=, c_actions=,
+d_values=, d_actions=, rewards=)``, the driver's pack-and-store as one launch. Generated noise is a stateless hash of
 a seed taken from torch's CPU generator (as ``replay_memory._rng_sample_seed``), not torch's
 device stream: after ``torch.manual_seed`` two runs are identical. One attribute beyond the
 reference's: ``last``, the device tensors ``q1``, ``q2``, ``q_target``, ``td`` and ``loss`` of
@@ -344,6 +345,11 @@ class Hybrid_TD3_Model():  # noqa: N801 (reference name)
         td_errors = torch.ones(size=[len(transitions), 1]).to(self.device)
 
         self.memory.add(td_errors, transitions)
+
+    def store_step(self, *, features, c_actions, d_values, d_actions, rewards):
+        """store_transition(cat([features.float(), c_actions, d_values, d_actions.float(),
+        rewards], 1)) without the casts, the cat and the ones: one launch (Memory.add_step)."""
+        self.memory.add_step(features, c_actions, d_values, d_actions, rewards)
 
     def choose_action(self, state, *, noise=None):
         self.Hybrid_Actor.eval()

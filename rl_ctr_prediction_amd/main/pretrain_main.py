@@ -148,7 +148,7 @@ def _parser():
     parser.add_argument("--valid_day", type=int, default=11, help="6, 7, 8, 9, 10, 11, 12")
     parser.add_argument("--test_day", type=int, default=12, help="6, 7, 8, 9, 10, 11, 12")
     parser.add_argument("--campaign_id", default="1458/", help="1458, 3358, 3386, 3427, 3476")
-    parser.add_argument("--model_name", default="FM", help="FM, FFM, DeepFM, IPNN, FNN, DCN")
+    parser.add_argument("--model_name", default="FM", help="LR, FM, FFM, DeepFM, IPNN, FNN, DCN")
     parser.add_argument("--latent_dims", type=int, default=8)
     parser.add_argument("--epoch", type=int, default=100)
     parser.add_argument("--learning_rate", type=float, default=1e-4)

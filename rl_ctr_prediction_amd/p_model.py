@@ -1,7 +1,7 @@
-"""FM, FFM, DeepFM, InnerPNN, FNN and DCN with the reference's construction API, on the HIP
-kernels.
+"""LR, FM, FFM, DeepFM, InnerPNN, FNN and DCN with the reference's construction API, on the
+HIP kernels.
 
-Drop-in for ``src/models/p_model.py`` (FM 28-57, FFM 59-100, InnerPNN 146-200, DeepFM 256-324,
+Drop-in for ``src/models/p_model.py`` (LR 9-26, FM 28-57, FFM 59-100, InnerPNN 146-200, DeepFM 256-324,
 FNN 326-373, DCN 376-435): identical constructor
 signatures, submodules created in the same order (so ``torch.manual_seed(s)`` gives the
 same initial weights as the reference) and identical state_dict keys, so the RL drivers'
@@ -68,6 +68,32 @@ class _FMPart(torch.autograd.Function):
         g_bias = hip_ops.tensor_sum(gz) if ctx.needs_input_grad[3] else None
         return (None, g_emb if ctx.needs_input_grad[1] else None,
                 g_lin if ctx.needs_input_grad[2] else None, g_bias, None)
+
+
+class _LRPart(torch.autograd.Function):
+    """z [B,1] = bias + sum_f lin[x_f] (p_model.py:23) on ctr_lr_forward. Backward: every
+    slot's gradient is gz[b]; summed per row in slot order through the sparse plan
+    (deterministic, as _FMPart), returned dense [V,1] like embedding_dense_backward."""
+
+    @staticmethod
+    def forward(ctx, x, lin, bias):
+        ctx.save_for_backward(x)
+        ctx.V = lin.shape[0]
+        return hip_ops.lr_forward(x, lin, bias, want_p=False)["z"].view(-1, 1)
+
+    @staticmethod
+    def backward(ctx, gz):
+        (x,) = ctx.saved_tensors
+        B, F = x.shape
+        gz = gz.reshape(-1).contiguous()
+        g_lin = None
+        if ctx.needs_input_grad[1]:
+            plan = hip_ops.SparsePlanBuffers(B * F, gz.device).build(x, ctx.V)
+            slot_g = gz.view(B, 1).expand(B, F).reshape(-1, 1).contiguous()  # dL/dw[x_bf] = gz[b]
+            rows, _ = hip_ops.segment_sum_rows(plan, slot_g)
+            g_lin, _ = hip_ops.rows_to_dense(plan, ctx.V, rows)
+        g_bias = hip_ops.tensor_sum(gz).view(1) if ctx.needs_input_grad[2] else None
+        return None, g_lin, g_bias
 
 
 class _LinearAct(torch.autograd.Function):
@@ -212,6 +238,23 @@ def mlp_forward(mlp: nn.Sequential, h: torch.Tensor, training: bool,
         h = _LinearAct.apply(h, lin.weight, lin.bias, relu, drop, seed_fn())
         i = j
     return h
+
+
+class LR(nn.Module):
+    """p_model.py:9-26. z = bias + sum_f w[x_f]; p = sigmoid(z)."""
+
+    def __init__(self, feature_nums, output_dim=1):
+        super().__init__()
+        if output_dim != 1:
+            raise NotImplementedError("LR: output_dim must be 1 (the reference's only use)")
+        self.linear = nn.Embedding(feature_nums, output_dim)
+        self.bias = nn.Parameter(torch.zeros((output_dim,)))
+
+    def forward(self, x):
+        if torch.is_grad_enabled() and any(p.requires_grad for p in self.parameters()):
+            return torch.sigmoid(_LRPart.apply(x, self.linear.weight, self.bias))
+        r = hip_ops.lr_forward(x, self.linear.weight.detach(), self.bias.detach())
+        return r["p"].view(-1, 1)
 
 
 class FM(nn.Module):

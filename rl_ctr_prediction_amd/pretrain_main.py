@@ -10,8 +10,8 @@ of the checkpoint four epochs back.
 
 Differences, all deliberate: the training step is the fused HIP step (FM, DeepFM and
 IPNN; FFM: FusedFFMTrainer, the same deferred-exact Adam over its F*V field-table rows;
-FNN and DCN: AutogradTrainer, the reference's own step — autograd over the HIP kernels and
-torch.optim.Adam — which also serves the other models for comparison; LR, W&D, OPNN and AFM
+LR, FNN and DCN: AutogradTrainer, the reference's own step — autograd over the HIP kernels and
+torch.optim.Adam — which also serves the other models for comparison; W&D, OPNN and AFM
 are out of scope); the batches are
 sliced from one device-resident copy of the data instead of 8 DataLoader worker
 processes; the rotating-checkpoint cleanup skips files that were never written (the
@@ -47,6 +47,8 @@ def setup_seed(seed):
 
 
 def get_model(model_name, feature_nums, field_nums, latent_dims):
+    if model_name == "LR":
+        return Model.LR(feature_nums)
     if model_name == "FM":
         return Model.FM(feature_nums, latent_dims)
     if model_name == "DeepFM":
@@ -60,16 +62,16 @@ def get_model(model_name, feature_nums, field_nums, latent_dims):
     if model_name == "DCN":
         return Model.DCN(feature_nums, field_nums, latent_dims)
     raise NotImplementedError(
-        f"{model_name}: FM, FFM, DeepFM, IPNN, FNN and DCN are built on HIP; "
-        "LR/W&D/OPNN/AFM are out of scope (SURVEY.md §2 row 7)")
+        f"{model_name}: LR, FM, FFM, DeepFM, IPNN, FNN and DCN are built on HIP; "
+        "of LR/W&D/OPNN/AFM (SURVEY.md §2 row 7) only LR is built")
 
 
 def make_trainer(model_name, model, learning_rate, weight_decay):
     """The training step of a model family: the fused HIP step where one exists (FM, DeepFM,
-    IPNN; FFM), else the reference's own step through autograd (FNN, DCN)."""
+    IPNN; FFM), else the reference's own step through autograd (LR, FNN, DCN)."""
     if model_name == "FFM":
         return FusedFFMTrainer(model, lr=learning_rate, weight_decay=weight_decay)
-    if model_name in ("FNN", "DCN"):
+    if model_name in ("LR", "FNN", "DCN"):
         return AutogradTrainer(model, lr=learning_rate, weight_decay=weight_decay)
     return FusedCTRTrainer(model, lr=learning_rate, weight_decay=weight_decay)
 
@@ -332,7 +334,7 @@ def _parser():
     parser.add_argument("--data_path", default="../../data/")
     parser.add_argument("--dataset_name", default="avazu/", help="ipinyou, cretio, yoyi, avazu")
     parser.add_argument("--campaign_id", default="avazu/", help="1458, 3358, 3386, 3427, 3476, avazu")
-    parser.add_argument("--model_name", default="FM", help="FM, FFM, DeepFM, IPNN, FNN, DCN")
+    parser.add_argument("--model_name", default="FM", help="LR, FM, FFM, DeepFM, IPNN, FNN, DCN")
     parser.add_argument("--latent_dims", type=int, default=10)
     parser.add_argument("--epoch", type=int, default=20)
     parser.add_argument("--learning_rate", type=float, default=1e-3)

@@ -83,6 +83,21 @@ class Memory(object):
                         transitions, td, self.epsilon, self.alpha)
         self.memory_counter += n
 
+    def add_step(self, features, c_actions, d_values, d_actions, rewards):
+        """add(ones, cat([features.float(), c_actions, d_values, d_actions.float(), rewards], 1))
+        — the driver's store of one batch — as one launch, bitwise the same memory and
+        priorities. features [n, F] and d_actions [n, 1] are int32 / int64; c_actions, d_values
+        [n, A] and rewards [n, 1] may be row-strided views."""
+        n = features.shape[0] if isinstance(features, torch.Tensor) and features.dim() == 2 else -1
+        if n < 0:
+            raise ValueError("add_step: features must be an integer [n, F] tensor")
+        if n > self.memory_size:
+            raise ValueError(f"add_step: {n} transitions do not fit a memory of {self.memory_size}")
+        hip_ops.per_store_step(self.memory, self.prioritys_,
+                               self.memory_counter % self.memory_size, features, c_actions,
+                               d_values, d_actions, rewards, self.epsilon, self.alpha)
+        self.memory_counter += n
+
     def _sample(self, batch_size, mode, seed, who):
         k, filled = self._check_k(batch_size, who)
         if mode == hip_ops.PER_STOCHASTIC and seed is None:
