@@ -122,10 +122,19 @@ int ctr_deepfm_head(const float* h, int64_t B, int H, const float* w_out, const 
  * C[M,N] = op(A)[M,K] . op(B)[K,N] with epilogue `epi` (enum ctr_epilogue).
  * trans_a = 0: A stored [M,K] (lda >= K); 1: A stored [K,M] (lda >= M).
  * trans_b = 0: B stored [K,N] (ldb >= N); 1: B stored [N,K] (ldb >= K)  (nn.Linear weight).
+ * K == 0 is allowed (A and B may then be NULL) and yields the epilogue of 0: zeros, bias[n],
+ * relu(bias[n]), ... Leading dimensions may exceed the extents; elements between a row's
+ * extent and its stride are never read (A, B, aux) nor written (C). The alignment of A, B
+ * and C and lda/ldb/ldc % 4 select a staging / store path (16-byte LDS-DMA and float4 stores,
+ * or register staging and scalar stores), never a result: the same operands give the same
+ * bits at any base address and leading dimension.
  * Dropout keeps element (m,n) iff hash(seed, offset + m*N + n) >= p*2^32 and scales by
  * 1/(1-p), where offset += (*step_ptr) << 32 when step_ptr != NULL (a per-step mask read
- * on the device, for HIP-graph replay). `scale` is used by CTR_EPI_GRAD_MASK. Split-K
- * (long K, few tiles) uses `ws`.
+ * on the device, for HIP-graph replay). The counter runs over the logical matrix (m*N + n,
+ * not m*ldc + n) in uint64 arithmetic mod 2^64; hash = the high 32 bits of the
+ * (counter+1)-th splitmix64 output for state `seed`; p*2^32 is formed in double from the
+ * fp32 p, clamped to 2^32 - 1 and truncated. `scale` is used by CTR_EPI_GRAD_MASK (aux is
+ * read at aux[m*ldaux + n], ldaux >= N). Split-K (long K, few tiles) uses `ws`.
  * Replaces: nn.Linear / ReLU / Dropout of DeepFM.mlp (p_model.py:276-293) and of
  * PG_model.Net.mlp (PG_model.py:41-51), forward and autograd backward (dX and dW). */
 int64_t ctr_gemm_f32_workspace_bytes(int trans_a, int trans_b, int64_t M, int64_t N, int64_t K);
@@ -173,7 +182,10 @@ int ctr_gemm_resolved_algo(int algo);
  * ctr_gemm_planes: C[M,N] = A.B with the ctr_gemm_f32 epilogues. Orientation per operand:
  *   a_rc = 0: A stored [M][K] (k contiguous)     a_rc = 1: A stored [K][M] (A^T product)
  *   b_rc = 0: B stored [N][K] (nn.Linear weight) b_rc = 1: B stored [K][N]
- * Storage must cover align_up(K, 32) along k, zero-padded. Outputs: C (fp32, ldc) and/or Cp
+ * Storage must cover align_up(K, 32) along k, zero-padded (K == 0: one all-zero k tile, the
+ * result is the epilogue of 0). ldc >= N and, for CTR_EPI_GRAD_MASK, ldaux >= N; C's
+ * alignment and ldc % 4 select a store path, never a result; the dropout counter is m*N + n
+ * as in ctr_gemm_f32. Outputs: C (fp32, ldc) and/or Cp
  * (the planes of the epilogue's result, for the next GEMM). Split-K scratch is sized by
  * ctr_gemm_planes_workspace_bytes. ctr_gemm_planes_config reports the tiling chosen
  * (tuning and tests). */

@@ -288,6 +288,11 @@ __global__ __launch_bounds__(WAVES_M* WAVES_N* KSPLIT * 64) void gemm_f32_kernel
       const int q = wave * IB + j;
       kB[j] = B_KC ? 4 * ((lane % CPR) ^ kc_swz<BK>(RPP * q + lane / CPR)) : (256 * q + 4 * lane) / BN;
     }
+    // A lane whose k is at or past ke in a tail tile loads its row's float4 at k = kb instead
+    // (zeroed in LDS before use). kb < ke whenever a tile is issued, kb is a multiple of 32 and
+    // a k-contiguous operand has K % 4 == 0 on this path, so that float4 is inside the operand
+    // for every slab — also when k-tile 0 is itself the tail (K < BK, or a last split-K slab
+    // shorter than BK), where the lane's own tile-0 address srcA[j] is already at k >= ke.
     auto issue = [&](int t) {
       const float* st = smem + (t % NS) * STAGE;
       const int64_t k0 = kb + (int64_t)t * BK;
@@ -295,13 +300,13 @@ __global__ __launch_bounds__(WAVES_M* WAVES_N* KSPLIT * 64) void gemm_f32_kernel
 #pragma unroll
       for (int j = 0; j < IA; ++j) {
         const float* src = srcA[j] + t * stepA;
-        if (tail && !(k0 + kA[j] < ke)) src = srcA[j];  // in-bounds; zeroed before use
+        if (tail && !(k0 + kA[j] < ke)) src = srcA[j] - (A_KC ? (int64_t)kA[j] : kA[j] * a.lda);
         glds16(src, __builtin_amdgcn_readfirstlane(lds_addr(st + (wave * IA + j) * 256)));
       }
 #pragma unroll
       for (int j = 0; j < IB; ++j) {
         const float* src = srcB[j] + t * stepB;
-        if (tail && !(k0 + kB[j] < ke)) src = srcB[j];
+        if (tail && !(k0 + kB[j] < ke)) src = srcB[j] - (B_KC ? (int64_t)kB[j] : kB[j] * a.ldb);
         glds16(src, __builtin_amdgcn_readfirstlane(lds_addr(st + A_IMG + (wave * IB + j) * 256)));
       }
     };

@@ -1074,7 +1074,8 @@ extern "C" int ctr_gemm_planes_lastcol(int a_rc, int b_rc, int64_t M, int64_t N,
               "ctr_gemm_planes: B planes must cover the (32-padded) operand, zero-padded");
   CTR_REQUIRE(epi != CTR_EPI_BIAS_RELU_DROP || (drop_p >= 0.f && drop_p < 1.f),
               "ctr_gemm_planes: drop_p out of range");
-  CTR_REQUIRE(epi != CTR_EPI_GRAD_MASK || aux, "ctr_gemm_planes: GRAD_MASK needs aux");
+  CTR_REQUIRE(epi != CTR_EPI_GRAD_MASK || (aux && ldaux >= N),
+              "ctr_gemm_planes: GRAD_MASK needs aux with ldaux >= N");
   CTR_REQUIRE((epi != CTR_EPI_BIAS && epi != CTR_EPI_BIAS_RELU && epi != CTR_EPI_BIAS_RELU_DROP) || bias,
               "ctr_gemm_planes: bias epilogue without bias");
   const bool arc = a_rc != 0, brc = b_rc != 0;
@@ -1105,7 +1106,9 @@ extern "C" int ctr_gemm_planes_lastcol(int a_rc, int b_rc, int64_t M, int64_t N,
   g.drop_thr = epi == CTR_EPI_BIAS_RELU_DROP
                    ? (uint32_t)std::min<double>((double)drop_p * 4294967296.0, 4294967295.0)
                    : 0u;
-  g.drop_scale = epi == CTR_EPI_BIAS_RELU_DROP ? 1.0f / (1.0f - drop_p) : 1.0f;
+  // formed in double and rounded once, as ctr_gemm_f32_ex does (the fp32 quotient is one ulp
+  // off for p = 0.15, 0.29, ...; the same for the models' p = 0.2 and 0.5)
+  g.drop_scale = epi == CTR_EPI_BIAS_RELU_DROP ? (float)(1.0 / (1.0 - (double)drop_p)) : 1.0f;
   g.seed = seed;
   g.offset = offset;
   g.step_ptr = step_ptr;
