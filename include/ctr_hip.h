@@ -61,9 +61,9 @@ int ctr_device_count(void);
 /* A stream whose kernels run only on the CUs set in mask[0 .. n_words) (bit c % 32 of word
  * c / 32 = CU c in the driver's numbering; hipExtStreamCreateWithCUMask), and its release.
  * The mask holds for launches on that stream, eager or as the root of a graph launched on
- * it, not for a graph branch forked onto it (tools/cumask_probe.hip). Used by the
- * weight-gradient side stream experiment (CTR_WGRAD_CU_FRAC); no reference
- * counterpart. */
+ * it, not for a graph branch forked onto it (tools/cumask_probe.hip). Measured and not
+ * kept: the weight-gradient side stream on it (CTR_WGRAD_CU_FRAC); no product
+ * code uses it any more. No reference counterpart. */
 int ctr_stream_create_cu_masked(const uint32_t* mask, int n_words, ctr_stream_t* out);
 int ctr_stream_destroy(ctr_stream_t stream);
 

@@ -39,18 +39,6 @@ typedef float pf32x4 __attribute__((ext_vector_type(4)));
 
 constexpr int kPBK = 32;  // k per LDS stage = one 16x16x32 MFMA
 
-// the software-pipelined stage of the k-contiguous x k-contiguous products with >= 4
-// 16-column groups per wave (fwd0's 64 x 160 tiling: B fragments of group tn+1 read under the
-// MFMAs of group tn, the DMA pieces spread between the groups): fwd0 69.2 -> 59.7 us
-// standalone at C3 (tools/gemm_planes_bench.py, profiles/r06_gemm_pipe.txt); fwd1's 32 x 32
-// waves (two groups) ran slower that way (17.4 -> 19.1 us) and keep the burst form
-#ifndef CTR_PL_PIPE
-#define CTR_PL_PIPE 1
-#endif
-#ifndef CTR_PL_PIPE2
-#define CTR_PL_PIPE2 0
-#endif
-
 struct PlaneSrc {
   const uint16_t* p;  // plane 0 (bf16 bits); planes `ps` elements apart
   int64_t ld;         // elements per storage row
@@ -151,43 +139,26 @@ __device__ __forceinline__ pbf16x8 frag_kc_at(const char* p) {
   return *reinterpret_cast<const pbf16x8*>(p);
 }
 
-// the same read as an asm statement (waited for by hand, CTR_PL_PIPE2)
-__device__ __forceinline__ pbf16x8 frag_kc_asm(const char* p) {
-  pbf16x8 v;
-  const uint32_t a = (uint32_t)(uintptr_t)(const CTR_LDS char*)p;
-  asm volatile("ds_read_b128 %0, %1" : "=v"(v) : "v"(a));
-  return v;
-}
-
-// The transpose reads as inline asm (CTR_PL_TR_ASM, default): with the builtin, hipcc 7.2
-// cannot tell the read from the LDS-DMA writes in flight and waits vmcnt(0) before it — the
-// next stage's DMA then lands before the current stage computes (no load/compute overlap in
-// any GEMM with a k-strided operand). The asm form is invisible to the wait pass, so its
-// results are waited for explicitly (planes_wait_lds) before the MFMAs that use them.
-#ifndef CTR_PL_TR_ASM
-#define CTR_PL_TR_ASM 1
-#endif
+// The transpose reads as inline asm: with the builtin
+// (__builtin_amdgcn_ds_read_tr16_b64_v4bf16), hipcc 7.2 cannot tell the read from the LDS-DMA
+// writes in flight and waits vmcnt(0) before it — the next stage's DMA then lands before the
+// current stage computes (no load/compute overlap in any GEMM with a k-strided operand). The
+// asm form is invisible to the wait pass, so its results are waited for explicitly
+// (planes_wait_lds) before the MFMAs that use them.
 __device__ __forceinline__ pbf16x8 frag_rc_at(const char* p0, const char* p1) {
-#if CTR_PL_TR_ASM
   pbf16x4 v0, v1;
   const uint32_t a0 = (uint32_t)(uintptr_t)(const CTR_LDS char*)p0;
   const uint32_t a1 = (uint32_t)(uintptr_t)(const CTR_LDS char*)p1;
   asm volatile("ds_read_b64_tr_b16 %0, %1" : "=v"(v0) : "v"(a0));
   asm volatile("ds_read_b64_tr_b16 %0, %1" : "=v"(v1) : "v"(a1));
-#else
-  const pbf16x4 v0 = __builtin_amdgcn_ds_read_tr16_b64_v4bf16((CTR_LDS pbf16x4*)p0);
-  const pbf16x4 v1 = __builtin_amdgcn_ds_read_tr16_b64_v4bf16((CTR_LDS pbf16x4*)p1);
-#endif
   return __builtin_shufflevector(v0, v1, 0, 1, 2, 3, 4, 5, 6, 7);
 }
 
 // every LDS read issued so far has landed (the asm transpose reads are not tracked by the
 // compiler), and no MFMA is hoisted above this point (cdna_hip_programming.md rule 18)
 __device__ __forceinline__ void planes_wait_lds() {
-#if CTR_PL_TR_ASM
   asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
   __builtin_amdgcn_sched_barrier(0);
-#endif
 }
 
 // ---- epilogue --------------------------------------------------------------------
@@ -449,100 +420,16 @@ __global__ __launch_bounds__(64 * WAVES_M* WAVES_N) void gemm_planes_kernel(Plan
   };
 
   constexpr int IPW = IPWA + IPWB;
-#if CTR_PL_PIPE2
-  if constexpr ((A_RC || B_RC) && KS == 1) {
-    // The pipelined stage for products with a k-strided operand: every fragment read is an
-    // asm statement (the compiler's wait pass cannot count the transpose reads, and its
-    // conservative lgkmcnt(0) for its own reads would drain them too), waited for by hand:
-    // the B fragments of group tn+1 are in flight (lgkmcnt(NBR)) under the MFMAs of group
-    // tn, and the next stage's DMA pieces are spread between the groups.
-    constexpr int NBR = 3 * (B_RC ? 2 : 1);
-    const int tlast = nt - 1;
-    auto issue_piece = [&](int j, int ts) {
-      char* st_ = smem + (ts % NS) * STAGE;
-      const int tsrc = min(ts, tlast);
-      if (j < IPWA)
-        __builtin_amdgcn_global_load_lds((const void*)((const char*)SA.p + (int64_t)tsrc * stepA + offA[j]),
-                                         (CTR_LDS void*)(st_ + ldsA[j]), 16, 0, 0);
-      else
-        __builtin_amdgcn_global_load_lds((const void*)((const char*)SB.p + (int64_t)tsrc * stepB + offB[j - IPWA]),
-                                         (CTR_LDS void*)(st_ + ldsB[j - IPWA]), 16, 0, 0);
-    };
-    if (nt > 0) {
-#pragma unroll
-      for (int s = 0; s < NS - 1; ++s)
-#pragma unroll
-        for (int j = 0; j < IPW; ++j) issue_piece(j, s);
-    }
-    for (int t = 0; t < nt; ++t) {
-      asm volatile("s_waitcnt vmcnt(%0)" ::"n"(IPW * (NS - 2)) : "memory");
-      __builtin_amdgcn_s_barrier();
-      asm volatile("" ::: "memory");
-      const char* st = smem + (t % NS) * STAGE;
-      if constexpr (NS <= 2) {  // a 2-deep ring: the next stage's pieces go out first
-#pragma unroll
-        for (int j = 0; j < IPW; ++j) issue_piece(j, t + NS - 1);
-      }
-      pbf16x8 af[TM][3], bf[2][3];
-#pragma unroll
-      for (int i = 0; i < TM; ++i)
-#pragma unroll
-        for (int p = 0; p < 3; ++p) {
-          const char* img = st + p * A_PL;
-          af[i][p] = A_RC ? frag_rc_at(img + aoff[i][0], img + aoff[i][1])
-                          : frag_kc_asm(img + aoff[i][0]);
-        }
-#pragma unroll
-      for (int p = 0; p < 3; ++p) {
-        const char* img = st + 3 * A_PL + p * B_PL;
-        bf[0][p] = B_RC ? frag_rc_at(img + boff[0][0], img + boff[0][1])
-                        : frag_kc_asm(img + boff[0][0]);
-      }
-#pragma unroll
-      for (int tn = 0; tn < TN; ++tn) {
-        const int cb = tn & 1;
-        if (tn + 1 < TN) {
-#pragma unroll
-          for (int p = 0; p < 3; ++p) {
-            const char* img = st + 3 * A_PL + p * B_PL;
-            bf[cb ^ 1][p] = B_RC ? frag_rc_at(img + boff[tn + 1][0], img + boff[tn + 1][1])
-                                 : frag_kc_asm(img + boff[tn + 1][0]);
-          }
-          asm volatile("s_waitcnt lgkmcnt(%0)" ::"n"(NBR) : "memory");
-        } else {
-          asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-        }
-        __builtin_amdgcn_sched_barrier(0);
-        if constexpr (NS > 2) {  // deeper rings: the pieces spread between the groups
-          const int j0 = (IPW * tn) / TN, j1 = (IPW * (tn + 1)) / TN;
-#pragma unroll
-          for (int j = 0; j < IPW; ++j)
-            if (j >= j0 && j < j1) issue_piece(j, t + NS - 1);
-        }
-#pragma unroll
-        for (int i = 0; i < TM; ++i) {
-          pf32x4 v = lo[i][tn];
-          v = __builtin_amdgcn_mfma_f32_16x16x32_bf16(af[i][1], bf[cb][1], v, 0, 0, 0);
-          v = __builtin_amdgcn_mfma_f32_16x16x32_bf16(af[i][0], bf[cb][2], v, 0, 0, 0);
-          v = __builtin_amdgcn_mfma_f32_16x16x32_bf16(af[i][2], bf[cb][0], v, 0, 0, 0);
-          v = __builtin_amdgcn_mfma_f32_16x16x32_bf16(af[i][0], bf[cb][1], v, 0, 0, 0);
-          v = __builtin_amdgcn_mfma_f32_16x16x32_bf16(af[i][1], bf[cb][0], v, 0, 0, 0);
-          lo[i][tn] = v;
-          acc[i][tn] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(af[i][0], bf[cb][0], acc[i][tn], 0, 0, 0);
-        }
-        __builtin_amdgcn_sched_barrier(0);
-      }
-    }
-  } else
-#endif
-#if CTR_PL_PIPE
   if constexpr (!A_RC && !B_RC && KS == 1 && TN >= 4) {
-    // Software-pipelined stage (both operands k-contiguous): the B fragments of 16-column
-    // group tn+1 are read while the MFMAs of group tn run, and the stage's LDS-DMA pieces
-    // for stage t+NS-1 are issued between the groups instead of in one burst at the
-    // barrier (the scheduler order is pinned by sched_group_barrier). The DMA is issued
-    // every iteration — past the last stage it re-loads the last stage into the ring slot
-    // nobody reads again — so the wait count is the constant IPW * (NS-2).
+    // Software-pipelined stage (both operands k-contiguous, >= 4 16-column groups per
+    // wave): the B fragments of group tn+1 are read while the MFMAs of group tn run, and the
+    // stage's LDS-DMA pieces for stage t+NS-1 are issued between the groups instead of in
+    // one burst at the barrier (the scheduler order is pinned by sched_group_barrier). The
+    // DMA is issued every iteration — past the last stage it re-loads the last stage into
+    // the ring slot nobody reads again — so the wait count is the constant IPW * (NS-2).
+    // fwd0 (64 x 160 tiling) 69.2 -> 59.7 us standalone at C3 (tools/gemm_planes_bench.py,
+    // profiles/r06_gemm_pipe.txt); fwd1's 32 x 32 waves (two groups) ran slower that way
+    // (17.4 -> 19.1 us) and keep the burst form
     const int tlast = nt - 1;
     auto issue_piece = [&](int j, int ts) {
       char* st_ = smem + (ts % NS) * STAGE;
@@ -605,7 +492,6 @@ __global__ __launch_bounds__(64 * WAVES_M* WAVES_N) void gemm_planes_kernel(Plan
       }
     }
   } else
-#endif
   {
   // prologue: stages 0 .. NS-2 in flight
 #pragma unroll
@@ -875,16 +761,12 @@ static PlCfg pl_choose(bool a_rc, bool b_rc, int64_t M, int64_t N, int64_t Kp) {
   // N <= 256 with K >= 512 (4096 x 256 x 512: tile 21 11.9 us vs 17.3 on 17), 320 < N <= 768
   // with K >= 1024 (4096 x 512 x 1024: tile 22 30.7 vs 35.0 on 16) — and a k-strided B with
   // K >= 512 on 128 x 128 tiles (4096 x 1024 x 512: tile 10 31.2 vs 33.6 on 7). The C3 shapes
-  // (K 300 / 320) keep their in-step-measured tilings. CTR_PL_RULES_R05=0: the round-4 rules.
-  static const bool r05 = [] {
-    const char* e = getenv("CTR_PL_RULES_R05");
-    return !(e && e[0] == '0');
-  }();
-  if (r05 && !a_rc && !b_rc && M >= 2048 && N <= 256 && Kp >= 512 && Kp % 64 == 0)
+  // (K 300 / 320) keep their in-step-measured tilings.
+  if (!a_rc && !b_rc && M >= 2048 && N <= 256 && Kp >= 512 && Kp % 64 == 0)
     return mk(21, 1);
-  if (r05 && !a_rc && !b_rc && M >= 2048 && N > 320 && N <= 768 && Kp >= 1024 && Kp % 64 == 0)
+  if (!a_rc && !b_rc && M >= 2048 && N > 320 && N <= 768 && Kp >= 1024 && Kp % 64 == 0)
     return mk(22, 1);
-  if (r05 && !a_rc && b_rc && M >= 2048 && N >= 1024 && N <= 1024 + 64 && Kp >= 512)
+  if (!a_rc && b_rc && M >= 2048 && N >= 1024 && N <= 1024 + 64 && Kp >= 512)
     return mk(10, 1);
   if (!a_rc && !b_rc && M >= 2048 && N <= 256) return mk(17, 1);
   if (!a_rc && b_rc && M >= 2048 && N >= 1024) {
@@ -916,7 +798,7 @@ static PlCfg pl_choose(bool a_rc, bool b_rc, int64_t M, int64_t N, int64_t Kp) {
     // (20 tiles) 24-32 splits 22.5-23 us vs 16 24
     // round 5: at K <= 4096 (the C4 policy weight gradients) ~600 blocks, 2-3 per CU — dW1
     // (128 tiles) 4 splits 35.5 us vs 10 41.6, dW0 (192 tiles) 4 splits 47.1 vs 7 53.9
-    const int64_t wg_blocks = (r05 && Kp <= 4096) ? 600 : 1170;
+    const int64_t wg_blocks = Kp <= 4096 ? 600 : 1170;
     const int64_t tiles = ceil_div(M, 64) * ceil_div(N, 64);
     const int s = (int)std::max<int64_t>(1, std::min<int64_t>(std::min<int64_t>(
                       ceil_div(wg_blocks, tiles), Kp / 256), 64));

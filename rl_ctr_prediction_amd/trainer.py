@@ -108,8 +108,7 @@ class InputSlot:
     reference trains on a new batch every iteration, all_main/pretrain_main.py:71-78)."""
 
     __slots__ = ("shape", "index", "ids", "y", "y_key", "plan", "ev", "plan_graph",
-                 "done_ev", "stream_i", "stage_stream", "cap", "counts", "slot2u", "gen",
-                 "planned")
+                 "done_ev", "stream_i", "stage_stream", "cap", "counts", "slot2u", "gen")
 
     def __init__(self, shape, index: int, device):
         B, F, dtype = shape
@@ -126,7 +125,6 @@ class InputSlot:
         self.cap = self.counts = None  # ShardedCTRTrainer: per-owner runs of the plan
         self.slot2u = None  # ShardedCTRTrainer: slot -> unique ordinal, built with the plan
         self.gen = 0  # ShardedCTRTrainer: staging generation (which contents the plan measured)
-        self.planned = True  # False: staged ids copied, plan not built yet (plan_in_graph)
 
 
 @dataclass
@@ -287,17 +285,11 @@ class FusedCTRTrainer:
         self._wgrad_stream = None
         if self.kind in _MLP_KINDS:
             self._wgrad_stream = self._side if self._side is not None else self._new_stream()
-            # experiment: the weight-gradient stream on a fraction of the
-            # CUs, so dW0 leaves the rest to the scatter beside it. The mask holds for eager
-            # launches only — a graph branch forked onto a masked stream runs on every CU
-            # (tools/cumask_probe.hip) — so it was measured with graphs off: C3 5.2-5.8 vs
-            # 13.1-13.3 M ex/s unmasked, the masked queue's kernels no longer overlapping the
-            # main queue's (profiles/r06_cumask.txt). Not a default.
-            frac = os.environ.get("CTR_WGRAD_CU_FRAC")
-            if frac:
-                n_cus = torch.cuda.get_device_properties(self.device).multi_processor_count
-                self._wgrad_stream = hip_ops.cu_masked_stream(
-                    hip_ops.cu_mask_words(n_cus, float(frac)), device=self.device)
+            # Measured and not kept: this stream on a fraction of the CUs (CTR_WGRAD_CU_FRAC,
+            # hip_ops.cu_masked_stream). The mask holds for eager launches only
+            # (tools/cumask_probe.hip), so graphs were off: C3 5.2-5.8 vs 13.1-13.3 M ex/s
+            # unmasked (profiles/r06_cumask.txt). The masked ExternalStream was
+            # never destroyed, and the run with it crashed in __cxa_finalize at exit.
         # the MLP weights' planes: rewritten by the dense Adam with every update
         # (ctr_adam_dense_planes), re-split from the fp32 parameters (the source of truth:
         # state_dict / load_state_dict see fp32) whenever those changed outside the trainer
@@ -324,34 +316,13 @@ class FusedCTRTrainer:
         # in one step and none in the next)
         self._stage_seq = 0
         self._extra_plan_streams: list = []
-        # where a lookahead plan starts: after everything enqueued before the step that
-        # stages it (False), or after that whole step (True). Traced at C3 (round 5, kernel
-        # trace of the timed region): a plan that starts with the step lands beside the
-        # backward's weight-gradient GEMMs on every other step (its 26 column-sort blocks hold
-        # 26 CUs for ~125 us, dW0's one-block-per-CU grid then runs a second wave: 84 -> 132
-        # us, the step 410 -> 462 us); started after the step it runs beside the next step's
-        # catch-up and gather (HBM- and latency-bound, no slowdown measured) and is ready a
-        # whole step before it is needed. CTR_PLAN_AFTER_STEP=0/1 overrides the default
-        # (on for the MLP kinds, whose steps are long against the plan; FM steps at C2 are
-        # about the plan's length)
-        env = os.environ.get("CTR_PLAN_AFTER_STEP")
-        self.plan_after_step = (env == "1") if env in ("0", "1") else False
-        self._ev_end = None
-        # opt-in (CTR_PLAN_IN_GRAPH=1): the next batch's plan inside this step's
-        # graph, on the side list between dW1 and the dX join; a staged batch is then only
-        # copied ahead. Traced at C3 (round 6, profiles/r06_c3_timelines.txt): a plan built on
-        # a plan stream lands wherever its queue lets it — beside dX (free), beside dW0 on some
-        # steps (+50 us), beside the next catch-up / gather on others — so the steps' walls
-        # spread 394-460 us. In the side list the column sort stretches to ~83 us beside dX
-        # and delays dW0 until after the scatter: every step 435-450 us (scatter 40 us alone
-        # instead of 84 beside dW0, dW0 66 alone instead of 85, but serial), C3 12.73 / 12.78
-        # / 12.92 vs 13.32 / 13.32 / 13.39 M ex/s off (alternating): off by default. FM (the
-        # plan on the side list beside the gather and scatter, joined before the tail: one
-        # graph launch per step instead of two) at C2: 37.9 / 40.0 / 47.7 / 39.8 vs 49.3 /
-        # 55.4 / 49.2 / 55.7 M ex/s off — the join costs the GPU more than the launch saves
-        env = os.environ.get("CTR_PLAN_IN_GRAPH")
-        self.plan_in_graph = (env == "1") and self.kind in _MLP_KINDS + ("FM",)
-        self._next_plan = None  # the staged slot whose plan the step being launched builds
+        # a lookahead plan starts after everything enqueued before the step that stages it.
+        # Measured and not kept (profiles/r06_c3_timelines.txt), both slower:
+        # started after that whole step instead (CTR_PLAN_AFTER_STEP; a plan that lands beside
+        # dW0 costs it 84 -> 132 us, yet C3 13.08 / 12.90 vs 13.19 / 13.19 M ex/s), and built
+        # inside the previous step's graph on the side list (CTR_PLAN_IN_GRAPH): C3 12.73 /
+        # 12.78 / 12.92 vs 13.32 / 13.32 / 13.39 M ex/s, C2 (FM) 37.9 / 40.0 / 47.7 / 39.8 vs
+        # 49.3 / 55.4 / 49.2 / 55.7
         # cross-step pipelining of the MLP kinds' weight-gradient tail (one process, deferred
         # mode): the largest weight gradient dW0 = dH1^T X and the MLP weights' Adam of step t
         # run at the START of step t+1's graph, on the side stream beside its catch-up and
@@ -649,78 +620,32 @@ class FusedCTRTrainer:
         if self._staged:  # staged for batches that did not come next: free their slots
             keep = {k for _, k in nk}
             for k in [k for k in self._staged if k not in keep]:
-                ev = self._staged.pop(k).ev
-                if ev is not None:  # None: planned in a step graph (main's order)
-                    main.wait_event(ev)  # its plan-stream writes come first
+                main.wait_event(self._staged.pop(k).ev)  # its plan-stream writes come first
         todo = [(n, k) for n, k in nk if k not in self._staged]
         have = slot is not None
         ev_start = None
         if todo:  # everything enqueued before this step (the last users of the slots)
             ev_start = self._start_event()
             ev_start.record(main)
-        # the next batch's plan in this step's graph (MLP kinds): its slot is only copied ahead
-        pig = (self.plan_in_graph and not self._pipe and self._side is not None
-               and self.deferred)
-        if have:  # copied (and planned) ahead
-            if slot.ev is not None:
-                main.wait_event(slot.ev)
-                slot.ev = None
-            if not slot.planned:  # copied ahead, no step planned it: build it here, first
-                self._plan_staged_now(slot, main)
+        if have:  # copied and planned ahead
+            main.wait_event(slot.ev)
+            slot.ev = None
         else:
             slot = self._acquire_slot(shape)
             slot.ids.copy_(x, non_blocking=True)
         if not (have and slot.y_key is not None and slot.y_key == self._xkey(y)):
             slot.y.copy_(y.reshape(-1), non_blocking=True)
         slot.y_key = None
-        nxt = None
-        if pig and nk:
-            n1, k1 = nk[0]
-            if k1 not in self._staged:  # stage (copy) it now: this step plans it
-                self._stage_ahead(n1, k1, shape, slot, ev_start, main, ny.get(k1), plan=False)
-                todo = [(n, k) for n, k in todo if k != k1]
-            nxt = self._staged[k1]
-            if nxt.planned:
-                nxt = None
-            elif nxt.ev is not None:
-                main.wait_event(nxt.ev)  # its ids copy
-                nxt.ev = None
-        self._next_plan = nxt
-        try:
-            if self.use_graphs and self.timing is None:
-                loss = self._graph_step(slot, mean_div, have)
-            else:
-                self.step_table.ensure(self.step_count + 1)
-                loss = self._launch(slot.ids, slot.y, mean_div, have, plan=slot.plan,
-                                    pipe=self._pipe_state(slot))
-                self._after_step()
-        finally:
-            self._next_plan = None
-        if nxt is not None:  # complete in main's order, after this step
-            nxt.planned = True
-        if todo and self.plan_after_step:  # the staged plans start after this whole step
-            if self._ev_end is None:
-                self._ev_end = torch.cuda.Event()
-            self._ev_end.record(main)
-            ev_start = self._ev_end
+        if self.use_graphs and self.timing is None:
+            loss = self._graph_step(slot, mean_div, have)
+        else:
+            self.step_table.ensure(self.step_count + 1)
+            loss = self._launch(slot.ids, slot.y, mean_div, have, plan=slot.plan,
+                                pipe=self._pipe_state(slot))
+            self._after_step()
         for n, k in todo:
-            self._stage_ahead(n, k, shape, slot, ev_start, main, ny.get(k), plan=not pig)
+            self._stage_ahead(n, k, shape, slot, ev_start, main, ny.get(k))
         return loss
-
-    def _plan_staged_now(self, s: InputSlot, main) -> None:
-        """The plan of a slot staged (copied) ahead that no step graph planned, on its
-        staging stream (after its copy), replayed from its own plan graph once captured; the
-        main stream waits for it."""
-        ps = s.stage_stream if s.stage_stream is not None else self._plan_stream
-        torch.cuda.set_stream(ps)
-        try:
-            self._plan_build_slot(s, ps)
-            ev = self._slot_event(s)
-            ev.record(ps)
-        finally:
-            torch.cuda.set_stream(main)
-        main.wait_event(ev)
-        s.planned = True
 
     def _plan_build_slot(self, s: InputSlot, ps) -> None:
         """On the current stream ps: slot s's plan (its own captured plan graph once it
@@ -797,11 +722,10 @@ class FusedCTRTrainer:
         return s
 
     def _stage_ahead(self, nx: torch.Tensor, key, shape, current: InputSlot, ev_start,
-                     main, ny: torch.Tensor | None = None, plan: bool = True) -> None:
+                     main, ny: torch.Tensor | None = None) -> None:
         """Copy ids nx into a free slot and build its sparse plan there, on the slot's plan
         stream, concurrently with the step just enqueued (replayed from the slot's own
-        plan graph once captured). plan=False: the copy only (plan_in_graph: the step
-        before the batch's own builds its plan inside its graph)."""
+        plan graph once captured)."""
         s = self._acquire_slot(shape, exclude=current, ahead=True)
         ps = self._stage_stream(s)
         ps.wait_event(ev_start)
@@ -822,9 +746,7 @@ class FusedCTRTrainer:
                 if ny.is_cuda:
                     ny.record_stream(ps)
                 s.y_key = self._xkey(ny)
-            s.planned = plan
-            if plan:
-                self._plan_build_slot(s, ps)
+            self._plan_build_slot(s, ps)
             ev = self._slot_event(s)
             ev.record(ps)
         finally:
@@ -932,10 +854,8 @@ class FusedCTRTrainer:
         mlp = getattr(self.model, "mlp", None)
         drops = tuple(float(mlp[i].p) for i in (2, 5)) if mlp is not None else ()
         pipe = self._pipe_state(slot)
-        nxt = self._next_plan
         key = (slot.shape, slot.index, mean_div, self.model.training, drops, have,
-               pipe[0], None if pipe[1] is None else (pipe[1][0].B, pipe[1][2]),
-               None if nxt is None else (nxt.shape, nxt.index))
+               pipe[0], None if pipe[1] is None else (pipe[1][0].B, pipe[1][2]))
         hit = self._graphs.get(key)
         if hit is None:
             # the real step (sizes every buffer), then the same launches captured
@@ -985,7 +905,6 @@ class FusedCTRTrainer:
         gv = self.grad_views
         step_hint = self.step_count + 1
         self._ev_wplanes = None
-        ev_nplan = None  # FM plan_in_graph: the next batch's plan, joined before the tail
         if self._side is not None:
             # the sparse plan is only needed from the scatter on: build it on a side stream
             # while the catch-up (plan-free, from the ids) and the forward run here.
@@ -1038,18 +957,6 @@ class FusedCTRTrainer:
                     b.ev_tail.record()
             if not self.plan_first:
                 plan()
-            nxt = self._next_plan
-            if nxt is not None and self.kind not in _MLP_KINDS:
-                # FM (plan_in_graph): the next batch's plan on the side list, beside this
-                # step's gather and scatter, joined before the step's tail: one graph launch
-                # per step instead of a step graph and a plan graph
-                self._side.wait_event(ev0)
-                with torch.cuda.stream(self._side):
-                    t_p = self._mark("plan")
-                    nxt.plan.build(nxt.ids, self.V)
-                    self._span("plan", t_p)
-                    ev_nplan = torch.cuda.Event()
-                    ev_nplan.record()
         else:
             t_plan = self._mark("plan")
             b.plan.build(x, self.V)  # rows of this batch (needed before the forward when deferred)
@@ -1122,8 +1029,6 @@ class FusedCTRTrainer:
                                    self.eps, self.weight_decay, step_dev=self.step_cur,
                                    table=self.step_table)
         self._span("adam", t)
-        if ev_nplan is not None:
-            hip_ops.current_stream().wait_event(ev_nplan)
         # the dense Adam where the dense gradient completes: on the weight-gradient stream
         # at one process (beside the embedding apply), after the exchange otherwise
         if tail:
@@ -1267,11 +1172,6 @@ class FusedCTRTrainer:
             # Linear(300,200): dW1 = dH2^T H1, db1 = colsum dH2 (H1's ones column)
             self._gemm_planes(b.dh2p, b.h1p, True, True, H2, H1, B,
                               out=gv["mlp.3.weight"], last_col=gv["mlp.3.bias"])
-            nxt = self._next_plan
-            if nxt is not None:  # the next batch's plan, beside dX (plan_in_graph)
-                t = self._mark("plan")
-                nxt.plan.build(nxt.ids, self.V)
-                self._span("plan", t)
             if side is not None:  # from dX on
                 side.wait_event(b.ev_dx)
             # the column-sum pair here, ahead of dW0: seg_chunk takes the CUs before dW0
