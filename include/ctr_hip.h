@@ -880,6 +880,107 @@ int ctr_td3_critic_loss(int64_t B, const float* q1, const float* q2, const float
 int ctr_soft_update_multi(int count, const ctr_soft_update_entry* table, int64_t max_numel,
                           double tau, ctr_stream_t stream);
 
+/* ------------------------------------------- v10 hybrid TD3 agent (csrc/td3_v10.hip) -----
+ * The small kernels of v10_Hybrid_TD3_model_PER.py. All fp32 with A <= 64 columns; a row takes
+ * the next power of two >= A lanes of a wave. Sums that cross blocks leave one partial per
+ * block in an order fixed by the sizes, and the next launch combines them in that order: the
+ * same inputs give the same bits. B < 2^31.
+ * ctr_td3v10_uniform: out[i] = u(seed, offset + i) in (0, 1), i < n:
+ *   u = ((float)(hash_u32(seed, 2 e) >> 8) + 0.5f) * 2^-24, the first uniform of
+ *   ctr_td3_noise's element e (take uniforms and normals of one seed from disjoint ranges).
+ * ctr_td3v10_heads: the action heads from the pre-activations pre_c, pre_d [B, A] (row stride
+ *   ldp), the unit normals noise_c, noise_d and the uniforms `uniform` (all [B, A] contiguous).
+ *   g = -log(-log(u + 1e-20) + 1e-20). By mode:
+ *     0 act:    c_means = tanh(pre_c); c_softmax = softmax(c + (0.2 n_c + c));
+ *               d_action = softmax(((d_q + (0.2 n_d + d_q)) + g) / temperature)   (lines 229-246)
+ *     1 plain:  c_means = tanh(pre_c); c_softmax = softmax(c_means);
+ *               d_action = softmax((d_q + g) / temperature)                       (line 526)
+ *     2 random: c_means = clamp(n_c, -1, 1); c_softmax = softmax(c_means);
+ *               d_action = softmax(n_d); pre_c, pre_d, uniform unused             (lines 395-402)
+ *     3 best:   c_means = tanh(pre_c); c_softmax = softmax(c_means); d_action is not written
+ *               and d_index = argmax(d_q + g) + 1                                 (lines 410-421)
+ *   d_index [B] (int64) = argmax(d_action) + 1, the LOWEST index among equal values.
+ *   c_softmax, d_action and d_index are optional.
+ * ctr_td3v10_rank_mask: to_next_state_c_actions / to_current_state_c_actions (lines 427-472)
+ *   without their loops. choose = argmax(d[b]) + 1 (lowest index among equal values); the rank
+ *   of column m is #{j: c_j > c_m} + #{j < m: c_j == c_m}; it is kept when rank < choose.
+ *   out_c[b, m] = kept ? clamp(v, -1, 1) : 0 with v = c + (0.2 noise + c) when noise ([B, A]
+ *   contiguous) is given, else c. d, c, out_c have row strides ldd, ldc, ldo; out_d (optional,
+ *   row stride ldo) receives a copy of d and keep (optional, [B, A] bytes) the mask: out_c and
+ *   out_d are the two action column blocks of a critic's input.
+ * ctr_td3v10_heads_backward: the actor loss's gradient at the heads' pre-activations from the
+ *   critic-input gradients g_c, g_d [B, A] (row stride ldg) of the c and d columns:
+ *   d_pre_c = ((keep ? g_c : 0) + reg 2 c / (B A)) (1 - c^2)  (mask, the clamp, which is the
+ *   identity on tanh's range, the regulariser reg * mean(c^2), tanh');
+ *   d_d_q = p (g_d - sum_j p_j g_d_j) / temperature + reg 2 d_q / (B A) with p = d_soft, the
+ *   softmax at `temperature`, and the regulariser reg * mean(d_q^2). The argmax and the rank
+ *   carry no gradient. c_means, d_soft, d_pre_c, d_d_q: [B, A] contiguous; d_q: row stride ldq.
+ * ctr_grad_sumsq, ctr_grad_clip_scale: torch's clip_grad_norm_ over `count` (<= 64) tensors.
+ *   table is a HOST array (it travels in the kernel arguments: gradients are new tensors at
+ *   every step and nothing is copied to the device for them); max_numel is the largest numel.
+ *   ctr_grad_sumsq leaves min(16, ceil(max_numel / 2048)) fp64 partial sums of squares per
+ *   tensor in ws (ctr_grad_clip_workspace_bytes(count) bytes, 8-byte aligned), each added in an
+ *   order fixed by the sizes. ctr_grad_clip_scale, given the same table and ws, adds the
+ *   partials in one fixed order in every block, norm = (float)sqrt(sum), writes it to norm_out
+ *   (a device scalar, optional) and multiplies every element by
+ *   min(1, max_norm / (norm + 1e-6)) in fp32.
+ * ctr_td3v10_store: rows i < n of transitions [n, T] (row stride ldt) go to slot
+ *   (start + i) % N of memory [N, T], n <= N; the slot's two priorities are OVERWRITTEN by
+ *   td2[i] ([n, 2] contiguous, Memory.add: one launch) or, when td2 is NULL, by
+ *   (seed, transitions[i, T-1]) with seed = 1 when the max of the WHOLE prio2 [N, 2] (both
+ *   columns, every row, taken before any row is written) is 0, else that max (store_transition,
+ *   lines 350-356). That form is two launches: per-block maxima into ws
+ *   (CTR_TD3V10_MAX_WS_BYTES, needed only here), which every block of the store launch
+ *   reduces; nothing returns to the host. seed_out (optional) receives seed.
+ * ctr_td3v10_sample: ctr_per_sample's stochastic select (the same kernels, workspace and key
+ *   formula) on the v10 memory: the priority of row i < n_valid is (|prio2[i, 0]| + eps)^alpha,
+ *   evaluated where the select, the minimum and isw = (p / min p)^(-beta) read it. Nothing is
+ *   written to prio2. ws: ctr_per_workspace_bytes(N, k).
+ * ctr_td3v10_keys: the selection keys of rows [0, n_valid), bitwise the ones ctr_td3v10_sample
+ *   orders by for `seed` (ctr_per_keys on the transformed priorities).
+ * ctr_td3v10_update: prio2[idx[i], 0] = td[i], i < k (the raw signed error; column 1 is not
+ *   touched; an index outside [0, N) is skipped).
+ * ctr_bn_eval_backward: the parameter gradients of an eval-mode BatchNorm1d,
+ *   dbeta = sum dy, dgamma = sum dy (x - running_mean) / sqrt(running_var + eps), over the B
+ *   rows in fp64 in a fixed order; no dx. */
+#define CTR_GRAD_CLIP_MAX_TENSORS 64
+#define CTR_TD3V10_MAX_WS_BYTES 4096
+typedef struct ctr_grad_entry {
+  float* grad; int64_t numel;
+} ctr_grad_entry;
+int ctr_td3v10_uniform(int64_t n, uint64_t seed, uint64_t offset, float* out,
+                       ctr_stream_t stream);
+int ctr_td3v10_heads(int64_t B, int A, int mode, const float* pre_c, const float* pre_d,
+                     int64_t ldp, const float* noise_c, const float* noise_d,
+                     const float* uniform, float temperature, float* c_means, float* c_softmax,
+                     float* d_action, int64_t* d_index, ctr_stream_t stream);
+int ctr_td3v10_rank_mask(int64_t B, int A, const float* d, int64_t ldd, const float* c,
+                         int64_t ldc, const float* noise, float* out_c, float* out_d, int64_t ldo,
+                         uint8_t* keep, ctr_stream_t stream);
+int ctr_td3v10_heads_backward(int64_t B, int A, const float* g_c, const float* g_d, int64_t ldg,
+                              const uint8_t* keep, const float* c_means, const float* d_q,
+                              int64_t ldq, const float* d_soft, float temperature, float reg,
+                              float* d_pre_c, float* d_d_q, ctr_stream_t stream);
+int64_t ctr_grad_clip_workspace_bytes(int count);
+int ctr_grad_sumsq(int count, const ctr_grad_entry* table, int64_t max_numel, void* ws,
+                   int64_t ws_bytes, ctr_stream_t stream);
+int ctr_grad_clip_scale(int count, const ctr_grad_entry* table, int64_t max_numel, float max_norm,
+                        const void* ws, int64_t ws_bytes, float* norm_out, ctr_stream_t stream);
+int ctr_td3v10_store(int64_t N, int T, int64_t start, int64_t n, const float* transitions,
+                     int64_t ldt, const float* td2, void* ws, int64_t ws_bytes,
+                     float* memory, float* prio2, float* seed_out, ctr_stream_t stream);
+int ctr_td3v10_keys(int64_t n_valid, const float* prio2, float eps, float alpha, uint64_t seed,
+                    float* keys, ctr_stream_t stream);
+int ctr_td3v10_sample(int64_t N, int T, int64_t n_valid, int k, uint64_t seed, float beta,
+                      float eps, float alpha, const float* memory, const float* prio2,
+                      int64_t* idx, float* batch, float* isw, float* min_p, void* ws,
+                      int64_t ws_bytes, ctr_stream_t stream);
+int ctr_td3v10_update(int64_t N, int64_t k, const int64_t* idx, const float* td, float* prio2,
+                      ctr_stream_t stream);
+int ctr_bn_eval_backward(int64_t B, int N, const float* dy, int64_t lddy, const float* x,
+                         int64_t ldx, const float* running_mean, const float* running_var,
+                         float eps, float* dgamma, float* dbeta, ctr_stream_t stream);
+
 /* ------------------------------------------------------ A8: REINFORCE (PG) -----------
  * ctr_softmax_rows: out[b,:] = softmax(x[b,:]) (PG_model.py:56).
  * ctr_pg_discount_norm: discounted return of an episode, reverse recurrence
@@ -1053,6 +1154,73 @@ typedef struct ctr_soft_update_multi_args {
   int count; const ctr_soft_update_entry* table; int64_t max_numel; double tau;
 } ctr_soft_update_multi_args;
 int ctr_op_soft_update_multi(const ctr_soft_update_multi_args* a, ctr_stream_t stream);
+
+/* The v10 agent's operations in struct form, each forwarding to its flat entry point. */
+typedef struct ctr_td3v10_uniform_args {
+  int64_t n; uint64_t seed; uint64_t offset; float* out;
+} ctr_td3v10_uniform_args;
+int ctr_op_td3v10_uniform(const ctr_td3v10_uniform_args* a, ctr_stream_t stream);
+
+typedef struct ctr_td3v10_heads_args {
+  int64_t B; int A; int mode; const float* pre_c; const float* pre_d; int64_t ldp;
+  const float* noise_c; const float* noise_d; const float* uniform; float temperature;
+  float* c_means; float* c_softmax; float* d_action; int64_t* d_index;
+} ctr_td3v10_heads_args;
+int ctr_op_td3v10_heads(const ctr_td3v10_heads_args* a, ctr_stream_t stream);
+
+typedef struct ctr_td3v10_rank_mask_args {
+  int64_t B; int A; const float* d; int64_t ldd; const float* c; int64_t ldc; const float* noise;
+  float* out_c; float* out_d; int64_t ldo; uint8_t* keep;
+} ctr_td3v10_rank_mask_args;
+int ctr_op_td3v10_rank_mask(const ctr_td3v10_rank_mask_args* a, ctr_stream_t stream);
+
+typedef struct ctr_td3v10_heads_backward_args {
+  int64_t B; int A; const float* g_c; const float* g_d; int64_t ldg; const uint8_t* keep;
+  const float* c_means; const float* d_q; int64_t ldq; const float* d_soft; float temperature;
+  float reg; float* d_pre_c; float* d_d_q;
+} ctr_td3v10_heads_backward_args;
+int ctr_op_td3v10_heads_backward(const ctr_td3v10_heads_backward_args* a, ctr_stream_t stream);
+
+typedef struct ctr_grad_sumsq_args {
+  int count; const ctr_grad_entry* table; int64_t max_numel; void* ws; int64_t ws_bytes;
+} ctr_grad_sumsq_args;
+int ctr_op_grad_sumsq(const ctr_grad_sumsq_args* a, ctr_stream_t stream);
+
+typedef struct ctr_grad_clip_scale_args {
+  int count; const ctr_grad_entry* table; int64_t max_numel; float max_norm; const void* ws;
+  int64_t ws_bytes; float* norm_out;
+} ctr_grad_clip_scale_args;
+int ctr_op_grad_clip_scale(const ctr_grad_clip_scale_args* a, ctr_stream_t stream);
+
+typedef struct ctr_td3v10_store_args {
+  int64_t N; int T; int64_t start; int64_t n; const float* transitions; int64_t ldt;
+  const float* td2; void* ws; int64_t ws_bytes; float* memory; float* prio2;
+  float* seed_out;
+} ctr_td3v10_store_args;
+int ctr_op_td3v10_store(const ctr_td3v10_store_args* a, ctr_stream_t stream);
+
+typedef struct ctr_td3v10_keys_args {
+  int64_t n_valid; const float* prio2; float eps; float alpha; uint64_t seed; float* keys;
+} ctr_td3v10_keys_args;
+int ctr_op_td3v10_keys(const ctr_td3v10_keys_args* a, ctr_stream_t stream);
+
+typedef struct ctr_td3v10_sample_args {
+  int64_t N; int T; int64_t n_valid; int k; uint64_t seed; float beta; float eps; float alpha;
+  const float* memory; const float* prio2; int64_t* idx; float* batch; float* isw; float* min_p;
+  void* ws; int64_t ws_bytes;
+} ctr_td3v10_sample_args;
+int ctr_op_td3v10_sample(const ctr_td3v10_sample_args* a, ctr_stream_t stream);
+
+typedef struct ctr_td3v10_update_args {
+  int64_t N; int64_t k; const int64_t* idx; const float* td; float* prio2;
+} ctr_td3v10_update_args;
+int ctr_op_td3v10_update(const ctr_td3v10_update_args* a, ctr_stream_t stream);
+
+typedef struct ctr_bn_eval_backward_args {
+  int64_t B; int N; const float* dy; int64_t lddy; const float* x; int64_t ldx;
+  const float* running_mean; const float* running_var; float eps; float* dgamma; float* dbeta;
+} ctr_bn_eval_backward_args;
+int ctr_op_bn_eval_backward(const ctr_bn_eval_backward_args* a, ctr_stream_t stream);
 
 #ifdef __cplusplus
 }

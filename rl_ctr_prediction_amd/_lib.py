@@ -164,13 +164,86 @@ class SoftUpdateMultiArgs(C.Structure):
     _fields_ = [("count", _i32), ("table", _vp), ("max_numel", _i64), ("tau", _f64)]
 
 
+class GradEntry(C.Structure):
+    """Mirror of ``ctr_grad_entry`` (include/ctr_hip.h): a HOST table row."""
+    _fields_ = [("grad", _vp), ("numel", _i64)]
+
+
+class Td3v10UniformArgs(C.Structure):
+    _fields_ = [("n", _i64), ("seed", _u64), ("offset", _u64), ("out", _vp)]
+
+
+class Td3v10HeadsArgs(C.Structure):
+    _fields_ = [("B", _i64), ("A", _i32), ("mode", _i32), ("pre_c", _vp), ("pre_d", _vp),
+                ("ldp", _i64), ("noise_c", _vp), ("noise_d", _vp), ("uniform", _vp),
+                ("temperature", _f32), ("c_means", _vp), ("c_softmax", _vp), ("d_action", _vp),
+                ("d_index", _vp)]
+
+
+class Td3v10RankMaskArgs(C.Structure):
+    _fields_ = [("B", _i64), ("A", _i32), ("d", _vp), ("ldd", _i64), ("c", _vp), ("ldc", _i64),
+                ("noise", _vp), ("out_c", _vp), ("out_d", _vp), ("ldo", _i64), ("keep", _vp)]
+
+
+class Td3v10HeadsBackwardArgs(C.Structure):
+    _fields_ = [("B", _i64), ("A", _i32), ("g_c", _vp), ("g_d", _vp), ("ldg", _i64),
+                ("keep", _vp), ("c_means", _vp), ("d_q", _vp), ("ldq", _i64), ("d_soft", _vp),
+                ("temperature", _f32), ("reg", _f32), ("d_pre_c", _vp), ("d_d_q", _vp)]
+
+
+class GradSumsqArgs(C.Structure):
+    _fields_ = [("count", _i32), ("table", _vp), ("max_numel", _i64), ("ws", _vp),
+                ("ws_bytes", _i64)]
+
+
+class GradClipScaleArgs(C.Structure):
+    _fields_ = [("count", _i32), ("table", _vp), ("max_numel", _i64), ("max_norm", _f32),
+                ("ws", _vp), ("ws_bytes", _i64), ("norm_out", _vp)]
+
+
+class Td3v10StoreArgs(C.Structure):
+    _fields_ = [("N", _i64), ("T", _i32), ("start", _i64), ("n", _i64), ("transitions", _vp),
+                ("ldt", _i64), ("td2", _vp), ("ws", _vp), ("ws_bytes", _i64),
+                ("memory", _vp), ("prio2", _vp), ("seed_out", _vp)]
+
+
+class Td3v10KeysArgs(C.Structure):
+    _fields_ = [("n_valid", _i64), ("prio2", _vp), ("eps", _f32), ("alpha", _f32), ("seed", _u64),
+                ("keys", _vp)]
+
+
+class Td3v10SampleArgs(C.Structure):
+    _fields_ = [("N", _i64), ("T", _i32), ("n_valid", _i64), ("k", _i32), ("seed", _u64),
+                ("beta", _f32), ("eps", _f32), ("alpha", _f32), ("memory", _vp), ("prio2", _vp),
+                ("idx", _vp), ("batch", _vp), ("isw", _vp), ("min_p", _vp), ("ws", _vp),
+                ("ws_bytes", _i64)]
+
+
+class Td3v10UpdateArgs(C.Structure):
+    _fields_ = [("N", _i64), ("k", _i64), ("idx", _vp), ("td", _vp), ("prio2", _vp)]
+
+
+class BnEvalBackwardArgs(C.Structure):
+    _fields_ = [("B", _i64), ("N", _i32), ("dy", _vp), ("lddy", _i64), ("x", _vp), ("ldx", _i64),
+                ("running_mean", _vp), ("running_var", _vp), ("eps", _f32), ("dgamma", _vp),
+                ("dbeta", _vp)]
+
+
+CTR_GRAD_CLIP_MAX_TENSORS = 64
+CTR_TD3V10_MAX_WS_BYTES = 4096
+
 OP_ARGS = {"fm_fwd": FmFwdArgs, "fm_bwd": FmBwdArgs, "deepfm_gather_concat": DeepfmGatherConcatArgs,
            "emb_scatter_add": EmbScatterAddArgs, "adam_dense": AdamDenseArgs,
            "adam_rowwise": AdamRowwiseArgs, "pairwise_fe": PairwiseFeArgs,
            "pg_returns": PgReturnsArgs, "bn_forward": BnForwardArgs,
            "bn_backward": BnBackwardArgs, "td3_noise": Td3NoiseArgs, "td3_act": Td3ActArgs,
            "td3_smooth": Td3SmoothArgs, "td3_critic_loss": Td3CriticLossArgs,
-           "soft_update_multi": SoftUpdateMultiArgs}
+           "soft_update_multi": SoftUpdateMultiArgs, "td3v10_uniform": Td3v10UniformArgs,
+           "td3v10_heads": Td3v10HeadsArgs, "td3v10_rank_mask": Td3v10RankMaskArgs,
+           "td3v10_heads_backward": Td3v10HeadsBackwardArgs, "grad_sumsq": GradSumsqArgs,
+           "grad_clip_scale": GradClipScaleArgs, "td3v10_store": Td3v10StoreArgs,
+           "td3v10_keys": Td3v10KeysArgs, "td3v10_sample": Td3v10SampleArgs,
+           "td3v10_update": Td3v10UpdateArgs, "bn_eval_backward": BnEvalBackwardArgs}
 
 
 # name -> (restype, argtypes); the list is the whole ABI and tests/test_abi.py checks it
@@ -315,6 +388,24 @@ SIGNATURES = {
     "ctr_td3_critic_loss": (_i32, [_i64, _vp, _vp, _vp, _vp, _vp, _i64, _vp, _f32, _vp, _vp, _vp,
                                    _vp, _vp, _vp]),
     "ctr_soft_update_multi": (_i32, [_i32, _vp, _i64, _f64, _vp]),
+    "ctr_td3v10_uniform": (_i32, [_i64, _u64, _u64, _vp, _vp]),
+    "ctr_td3v10_heads": (_i32, [_i64, _i32, _i32, _vp, _vp, _i64, _vp, _vp, _vp, _f32, _vp, _vp,
+                                _vp, _vp, _vp]),
+    "ctr_td3v10_rank_mask": (_i32, [_i64, _i32, _vp, _i64, _vp, _i64, _vp, _vp, _vp, _i64, _vp,
+                                    _vp]),
+    "ctr_td3v10_heads_backward": (_i32, [_i64, _i32, _vp, _vp, _i64, _vp, _vp, _vp, _i64, _vp,
+                                         _f32, _f32, _vp, _vp, _vp]),
+    "ctr_grad_clip_workspace_bytes": (_i64, [_i32]),
+    "ctr_grad_sumsq": (_i32, [_i32, _vp, _i64, _vp, _i64, _vp]),
+    "ctr_grad_clip_scale": (_i32, [_i32, _vp, _i64, _f32, _vp, _i64, _vp, _vp]),
+    "ctr_td3v10_store": (_i32, [_i64, _i32, _i64, _i64, _vp, _i64, _vp, _vp, _i64, _vp, _vp, _vp,
+                                _vp]),
+    "ctr_td3v10_keys": (_i32, [_i64, _vp, _f32, _f32, _u64, _vp, _vp]),
+    "ctr_td3v10_sample": (_i32, [_i64, _i32, _i64, _i32, _u64, _f32, _f32, _f32, _vp, _vp, _vp,
+                                 _vp, _vp, _vp, _vp, _i64, _vp]),
+    "ctr_td3v10_update": (_i32, [_i64, _i64, _vp, _vp, _vp, _vp]),
+    "ctr_bn_eval_backward": (_i32, [_i64, _i32, _vp, _i64, _vp, _i64, _vp, _vp, _f32, _vp, _vp,
+                                    _vp]),
     "ctr_softmax_rows": (_i32, [_vp, _i64, _i32, _vp, _vp]),
     "ctr_pg_workspace_bytes": (_i64, [_i64]),
     "ctr_pg_discount_norm": (_i32, [_vp, _i64, _f64, _vp, _vp, _vp, _vp, _i64, _vp]),

@@ -107,6 +107,28 @@ __device__ __forceinline__ void per_ld4(const float* __restrict__ prio, int64_t 
   for (int j = 0; j < 4; ++j) p[j] = i0 + j < n ? prio[i0 + j] : 0.f;
 }
 
+// The v10 memory's priorities (csrc/td3_v10.hip): prio2 is [N, 2] (signed TD error, reward) and
+// the priority of row i is (|prio2[i, 0]| + eps) ^ alpha, evaluated where it is read. Rows
+// i0 .. i0+3, 0 past n. VEC: prio2 16-byte aligned (i0 is a multiple of 4: 32 bytes a thread).
+template <bool VEC>
+__device__ __forceinline__ void per_ld4_v10(const float* __restrict__ prio2, int64_t i0,
+                                            int64_t n, float eps, float alpha, float (&p)[4]) {
+  float raw[4];
+  if (VEC && i0 + 3 < n) {
+    const float4 a = *reinterpret_cast<const float4*>(prio2 + 2 * i0);
+    const float4 b = *reinterpret_cast<const float4*>(prio2 + 2 * i0 + 4);
+    raw[0] = a.x;
+    raw[1] = a.z;
+    raw[2] = b.x;
+    raw[3] = b.z;
+  } else {
+#pragma unroll
+    for (int j = 0; j < 4; ++j) raw[j] = i0 + j < n ? prio2[2 * (i0 + j)] : 0.f;
+  }
+#pragma unroll
+  for (int j = 0; j < 4; ++j) p[j] = i0 + j < n ? per_priority(raw[j], eps, alpha) : 0.f;
+}
+
 // one count into the block's LDS histogram; bin < 0: none. Called by whole waves. A wave whose
 // lanes all hold one bin (equal priorities) adds once instead of 64 times to one address.
 __device__ __forceinline__ void per_hist_add(int32_t* h, int bin) {
@@ -210,13 +232,16 @@ __global__ __launch_bounds__(kPerThreads) void per_update_kernel(
   }
 }
 
+// V10: prio is the v10 memory's [N, 2] tensor, transformed where it is read (per_ld4_v10)
+template <bool V10>
 __global__ __launch_bounds__(kPerThreads) void per_keys_kernel(int64_t n,
                                                                const float* __restrict__ prio,
-                                                               int mode, uint64_t seed,
+                                                               int mode, uint64_t seed, float eps,
+                                                               float alpha,
                                                                float* __restrict__ keys) {
   const int64_t step = (int64_t)gridDim.x * kPerThreads;
   for (int64_t i = (int64_t)blockIdx.x * kPerThreads + threadIdx.x; i < n; i += step)
-    keys[i] = per_key(prio[i], mode, seed, i);
+    keys[i] = per_key(V10 ? per_priority(prio[2 * i], eps, alpha) : prio[i], mode, seed, i);
 }
 
 // --------------------------------------------------------------------- selection ------
@@ -238,11 +263,11 @@ __device__ __forceinline__ void per_ldu4(const uint32_t* __restrict__ ukeys, int
 // Pass `pass` (0, 1, 2) of the radix select over the block's index range [b * chunk, ..).
 // FIRST (pass 0) computes the keys from prio and keeps their uint32 images in ukeys; the
 // later passes and the compaction stream those 4 n_valid bytes instead of recomputing them.
-template <bool VEC, bool FIRST>
+template <bool VEC, bool FIRST, bool V10 = false>
 __global__ __launch_bounds__(kPerThreads) void per_hist_kernel(
     int64_t n, int64_t chunk, const float* __restrict__ prio, int mode, uint64_t seed, int pass,
-    const PerState* __restrict__ st, uint32_t* __restrict__ ukeys, int32_t* __restrict__ hist,
-    float* __restrict__ blockmin) {
+    float eps, float alpha, const PerState* __restrict__ st, uint32_t* __restrict__ ukeys,
+    int32_t* __restrict__ hist, float* __restrict__ blockmin) {
   __shared__ int32_t h[kPerBins];
   __shared__ float red[kPerThreads / kWave];
   const int tid = threadIdx.x;
@@ -260,7 +285,11 @@ __global__ __launch_bounds__(kPerThreads) void per_hist_kernel(
     uint32_t u[4];
     if (FIRST) {
       float p[4];
-      per_ld4<VEC>(prio, i0, hi, p);
+      if constexpr (V10) {
+        per_ld4_v10<VEC>(prio, i0, hi, eps, alpha, p);
+      } else {
+        per_ld4<VEC>(prio, i0, hi, p);
+      }
 #pragma unroll
       for (int j = 0; j < 4; ++j) {
         u[j] = 0u;
@@ -448,10 +477,11 @@ __global__ __launch_bounds__(kPerThreads) void per_rank_kernel(int k,
 }
 
 // batch[r, :] = memory[idx[r], :], isw[r] = (prio[idx[r]] / min_p) ^ (-beta)
-template <bool VEC>
+template <bool VEC, bool V10 = false>
 __global__ __launch_bounds__(kPerThreads) void per_gather_kernel(
     int64_t N, int T, int k, const float* __restrict__ memory, const float* __restrict__ prio,
-    const int64_t* __restrict__ idx, float beta, const PerState* __restrict__ st,
+    const int64_t* __restrict__ idx, float beta, float eps, float alpha,
+    const PerState* __restrict__ st,
     float* __restrict__ batch, float* __restrict__ isw, float* __restrict__ min_p) {
 #pragma clang fp contract(off)
   const int cols = VEC ? T / 4 : T;
@@ -468,7 +498,8 @@ __global__ __launch_bounds__(kPerThreads) void per_gather_kernel(
     } else {
       batch[r * T + c] = memory[row * T + c];
     }
-    if (c == 0) isw[r] = powf(prio[row] / mp, -beta);
+    if (c == 0)
+      isw[r] = powf((V10 ? per_priority(prio[2 * row], eps, alpha) : prio[row]) / mp, -beta);
     if (it == 0 && min_p) min_p[0] = mp;
   }
 }
@@ -590,30 +621,45 @@ extern "C" int ctr_per_keys(int64_t n_valid, const float* prio, int mode, uint64
   if (rc != CTR_OK) return rc;
   if (n_valid == 0) return CTR_OK;
   CTR_REQUIRE(prio && keys, "ctr_per_keys: null prio / keys");
-  hipLaunchKernelGGL(per_keys_kernel, per_grid(n_valid), kPerThreads, 0, as_stream(stream),
-                     n_valid, prio, mode, seed, keys);
+  hipLaunchKernelGGL(per_keys_kernel<false>, per_grid(n_valid), kPerThreads, 0, as_stream(stream),
+                     n_valid, prio, mode, seed, 0.f, 0.f, keys);
   CTR_LAUNCH_CHECK("ctr_per_keys");
   return CTR_OK;
 }
 
-extern "C" int ctr_per_sample(int64_t N, int T, int64_t n_valid, int k, int mode, uint64_t seed,
-                              float beta, const float* memory, const float* prio, int64_t* idx,
-                              float* batch, float* isw, float* min_p, void* ws, int64_t ws_bytes,
-                              ctr_stream_t stream) {
-  int rc = per_check_sizes("ctr_per_sample", N, T);
+extern "C" int ctr_td3v10_keys(int64_t n_valid, const float* prio2, float eps, float alpha,
+                               uint64_t seed, float* keys, ctr_stream_t stream) {
+  CTR_REQUIRE(n_valid >= 0 && n_valid <= INT32_MAX,
+              "ctr_td3v10_keys: n_valid=%lld outside [0, 2^31)", (long long)n_valid);
+  if (n_valid == 0) return CTR_OK;
+  CTR_REQUIRE(prio2 && keys, "ctr_td3v10_keys: null prio2 / keys");
+  hipLaunchKernelGGL(per_keys_kernel<true>, per_grid(n_valid), kPerThreads, 0, as_stream(stream),
+                     n_valid, prio2, kPerStochastic, seed, eps, alpha, keys);
+  CTR_LAUNCH_CHECK("ctr_td3v10_keys");
+  return CTR_OK;
+}
+
+// The select, shared by ctr_per_sample (prio [N], V10 false: the code it always ran) and
+// ctr_td3v10_sample (prio [N, 2], transformed where it is read by eps and alpha).
+template <bool V10>
+static int per_sample_impl(const char* who, int64_t N, int T, int64_t n_valid, int k, int mode,
+                           uint64_t seed, float beta, float eps, float alpha, const float* memory,
+                           const float* prio, int64_t* idx, float* batch, float* isw,
+                           float* min_p, void* ws, int64_t ws_bytes, ctr_stream_t stream) {
+  int rc = per_check_sizes(who, N, T);
   if (rc != CTR_OK) return rc;
-  rc = per_check_mode("ctr_per_sample", mode);
+  rc = per_check_mode(who, mode);
   if (rc != CTR_OK) return rc;
-  CTR_REQUIRE(n_valid >= 0 && n_valid <= N, "ctr_per_sample: n_valid=%lld outside [0, N=%lld]",
+  CTR_REQUIRE(n_valid >= 0 && n_valid <= N, "%s: n_valid=%lld outside [0, N=%lld]", who,
               (long long)n_valid, (long long)N);
   CTR_REQUIRE(k >= 1 && k <= kPerMaxK && k <= n_valid,
-              "ctr_per_sample: k=%d outside [1, min(n_valid=%lld, %d)]", k, (long long)n_valid,
+              "%s: k=%d outside [1, min(n_valid=%lld, %d)]", who, k, (long long)n_valid,
               kPerMaxK);
   CTR_REQUIRE(memory && prio && idx && batch && isw,
-              "ctr_per_sample: null memory / prio / idx / batch / isw");
+              "%s: null memory / prio / idx / batch / isw", who);
   const int64_t need = ctr_per_workspace_bytes(N, k);
   if (!ws || ws_bytes < need || !per_al16(ws)) {
-    set_error("ctr_per_sample: workspace %lld < %lld bytes (or not 16-B aligned)",
+    set_error("%s: workspace %lld < %lld bytes (or not 16-B aligned)", who,
               (long long)ws_bytes, (long long)need);
     return CTR_ERR_WORKSPACE;
   }
@@ -634,17 +680,17 @@ extern "C" int ctr_per_sample(int64_t N, int T, int64_t n_valid, int k, int mode
   const int nblk = (int)ceil_div(tiles, tiles_per_block);
   const int64_t chunk = tiles_per_block * kPerTile;
   if (per_al16(prio)) {
-    hipLaunchKernelGGL((per_hist_kernel<true, true>), nblk, kPerThreads, 0, st, n_valid, chunk,
-                       prio, mode, seed, 0, state, ukeys, hist, blockmin);
+    hipLaunchKernelGGL((per_hist_kernel<true, true, V10>), nblk, kPerThreads, 0, st, n_valid,
+                       chunk, prio, mode, seed, 0, eps, alpha, state, ukeys, hist, blockmin);
   } else {
-    hipLaunchKernelGGL((per_hist_kernel<false, true>), nblk, kPerThreads, 0, st, n_valid, chunk,
-                       prio, mode, seed, 0, state, ukeys, hist, blockmin);
+    hipLaunchKernelGGL((per_hist_kernel<false, true, V10>), nblk, kPerThreads, 0, st, n_valid,
+                       chunk, prio, mode, seed, 0, eps, alpha, state, ukeys, hist, blockmin);
   }
   hipLaunchKernelGGL(per_pick_kernel, 1, kPerThreads, 0, st, 0, k, nblk, hist, blockmin, state);
   for (int pass = 1; pass < 3; ++pass) {
     int32_t* hp = hist + pass * kPerBins;
     hipLaunchKernelGGL((per_hist_kernel<true, false>), nblk, kPerThreads, 0, st, n_valid, chunk,
-                       prio, mode, seed, pass, state, ukeys, hp, blockmin);
+                       prio, mode, seed, pass, eps, alpha, state, ukeys, hp, blockmin);
     hipLaunchKernelGGL(per_pick_kernel, 1, kPerThreads, 0, st, pass, k, nblk, hp, blockmin,
                        state);
   }
@@ -657,12 +703,42 @@ extern "C" int ctr_per_sample(int64_t N, int T, int64_t n_valid, int k, int mode
                      idx);
   const bool gvec = T % 4 == 0 && per_al16(memory) && per_al16(batch);
   if (gvec) {
-    hipLaunchKernelGGL(per_gather_kernel<true>, per_grid((int64_t)k * (T / 4)), kPerThreads, 0,
-                       st, N, T, k, memory, prio, idx, beta, state, batch, isw, min_p);
+    hipLaunchKernelGGL((per_gather_kernel<true, V10>), per_grid((int64_t)k * (T / 4)),
+                       kPerThreads, 0, st, N, T, k, memory, prio, idx, beta, eps, alpha, state,
+                       batch, isw, min_p);
   } else {
-    hipLaunchKernelGGL(per_gather_kernel<false>, per_grid((int64_t)k * T), kPerThreads, 0, st, N,
-                       T, k, memory, prio, idx, beta, state, batch, isw, min_p);
+    hipLaunchKernelGGL((per_gather_kernel<false, V10>), per_grid((int64_t)k * T), kPerThreads, 0,
+                       st, N, T, k, memory, prio, idx, beta, eps, alpha, state, batch, isw, min_p);
   }
-  CTR_LAUNCH_CHECK("ctr_per_sample");
+  CTR_LAUNCH_CHECK(who);
   return CTR_OK;
+}
+
+extern "C" int ctr_per_sample(int64_t N, int T, int64_t n_valid, int k, int mode, uint64_t seed,
+                              float beta, const float* memory, const float* prio, int64_t* idx,
+                              float* batch, float* isw, float* min_p, void* ws, int64_t ws_bytes,
+                              ctr_stream_t stream) {
+  return per_sample_impl<false>("ctr_per_sample", N, T, n_valid, k, mode, seed, beta, 0.f, 0.f,
+                                memory, prio, idx, batch, isw, min_p, ws, ws_bytes, stream);
+}
+
+extern "C" int ctr_td3v10_sample(int64_t N, int T, int64_t n_valid, int k, uint64_t seed,
+                                 float beta, float eps, float alpha, const float* memory,
+                                 const float* prio2, int64_t* idx, float* batch, float* isw,
+                                 float* min_p, void* ws, int64_t ws_bytes, ctr_stream_t stream) {
+  return per_sample_impl<true>("ctr_td3v10_sample", N, T, n_valid, k, kPerStochastic, seed, beta,
+                               eps, alpha, memory, prio2, idx, batch, isw, min_p, ws, ws_bytes,
+                               stream);
+}
+
+extern "C" int ctr_op_td3v10_keys(const ctr_td3v10_keys_args* a, ctr_stream_t stream) {
+  CTR_REQUIRE(a, "ctr_op_td3v10_keys: null argument struct");
+  return ctr_td3v10_keys(a->n_valid, a->prio2, a->eps, a->alpha, a->seed, a->keys, stream);
+}
+
+extern "C" int ctr_op_td3v10_sample(const ctr_td3v10_sample_args* a, ctr_stream_t stream) {
+  CTR_REQUIRE(a, "ctr_op_td3v10_sample: null argument struct");
+  return ctr_td3v10_sample(a->N, a->T, a->n_valid, a->k, a->seed, a->beta, a->eps, a->alpha,
+                           a->memory, a->prio2, a->idx, a->batch, a->isw, a->min_p, a->ws,
+                           a->ws_bytes, stream);
 }

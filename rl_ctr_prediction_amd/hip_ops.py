@@ -17,7 +17,7 @@ import torch
 from ._lib import (CTR_EFLAG_CAPACITY, CTR_EFLAG_INDEX, CTR_ENSEMBLE_TIE_REWARDS, CTR_IDX_I32, CTR_IDX_I64, CTR_LABEL_F32,
                    CTR_LABEL_I32, CTR_LABEL_I64, EPI_BIAS, EPI_BIAS_RELU,
                    EPI_BIAS_RELU_DROP, EPI_GRAD_MASK, EPI_NONE, PlanesDesc, PlaneViewDesc, SparsePlan,
-                   CtrHipError, lib)
+                   CtrHipError, GradEntry, lib)
 
 __all__ = [
     "embedding_gather", "fm_forward", "fm_forward_planes", "bce_sigmoid", "deepfm_head", "gemm", "linear",
@@ -32,6 +32,9 @@ __all__ = [
     "bn_forward", "bn_backward", "td3_noise", "td3_act", "td3_smooth", "td3_critic_loss",
     "SoftUpdateTable", "soft_update_multi", "TD3_NOISE_NONE", "TD3_NOISE_PTR", "TD3_NOISE_SEED",
     "TD3_MAX_A",
+    "td3v10_uniform", "td3v10_heads", "td3v10_rank_mask", "td3v10_heads_backward",
+    "clip_grad_norm_", "td3v10_add", "td3v10_store_seeded", "td3v10_keys", "td3v10_sample", "td3v10_update",
+    "bn_eval_backward", "V10_ACT", "V10_PLAIN", "V10_RANDOM", "V10_BEST", "GRAD_CLIP_MAX_TENSORS",
     "AdamStepTable", "adam_deferred_rows", "adam_deferred_flush", "adam_deferred_catchup_ids",
     "step_begin", "step_end", "ids_add_", "shard_pack_ids", "shard_runs_copy",
     "softmax_rows", "pg_discount_norm", "pg_loss_grad", "pg_vt_mean", "pg_loss_grad_global", "check_index_error", "Workspace",
@@ -1806,6 +1809,285 @@ def soft_update_multi(table: SoftUpdateTable, tau: float) -> None:
         return
     lib.ctr_soft_update_multi(table.count, _p(table.table), table.max_numel, float(tau),
                               _stream())
+
+
+# ------------------------------------------ v10 hybrid TD3 agent (csrc/td3_v10.hip) ----
+V10_ACT, V10_PLAIN, V10_RANDOM, V10_BEST = 0, 1, 2, 3
+GRAD_CLIP_MAX_TENSORS = 64
+_V10_MAX_WS_BYTES = 4096
+
+
+def _ba(t, name: str, B: int, A: int):
+    """An optional contiguous float32 [B, A] device tensor."""
+    if t is not None:
+        _f32(t, name)
+        if tuple(t.shape) != (B, A):
+            raise ValueError(f"{name}: must be [{B}, {A}], got {tuple(t.shape)}")
+    return t
+
+
+def td3v10_uniform(n: int, seed: int, offset: int = 0, out: torch.Tensor | None = None,
+                   device=None) -> torch.Tensor:
+    """n uniforms in (0, 1), elements offset .. offset + n - 1 of stream `seed`: the first
+    uniform of td3_noise's element (draw normals and uniforms of one seed from disjoint ranges)."""
+    if out is None:
+        out = torch.empty(n, dtype=torch.float32, device=device if device is not None else "cuda")
+    _f32(out, "out")
+    if out.numel() < n:
+        raise ValueError("td3v10_uniform: out is shorter than n")
+    lib.ctr_td3v10_uniform(n, int(seed) & (2**64 - 1), int(offset) & (2**64 - 1), _p(out),
+                           _stream())
+    return out
+
+
+def td3v10_heads(mode: int, pre_c=None, pre_d=None, *, noise_c=None, noise_d=None, uniform=None,
+                 temperature: float = 1.0, want_softmax: bool = True, want_index: bool = True):
+    """The v10 action heads in one launch (include/ctr_hip.h, ctr_td3v10_heads):
+    dict(c_means, c_softmax, d_action, d_index [B, 1] int64 = argmax + 1, lowest index on ties).
+    mode V10_ACT (exploration noise and Gumbel at `temperature`), V10_PLAIN (Gumbel softmax of
+    the bare heads), V10_RANDOM (actions from the normals alone; pre_c / pre_d unused) or
+    V10_BEST (no d_action; the index of the largest d_q + Gumbel)."""
+    if mode not in (V10_ACT, V10_PLAIN, V10_RANDOM, V10_BEST):
+        raise ValueError(f"td3v10_heads: unknown mode {mode}")
+    if mode == V10_RANDOM:
+        if noise_c is None or noise_c.dim() != 2:
+            raise ValueError("td3v10_heads: the random mode needs noise_c, noise_d [B, A]")
+        _dev(noise_c, "noise_c")
+        B, A = noise_c.shape
+        ldp = A
+        pre_c = pre_d = uniform = None
+    else:
+        ldp = _ld2(pre_c, "pre_c")
+        B, A = pre_c.shape
+        if tuple(pre_d.shape) != (B, A) or _ld2(pre_d, "pre_d") != ldp:
+            raise ValueError("td3v10_heads: pre_c and pre_d must have one shape and row stride")
+        if uniform is None:
+            raise ValueError("td3v10_heads: uniform [B, A] is needed (the Gumbel draw)")
+    if not 1 <= A <= TD3_MAX_A:
+        raise ValueError(f"td3v10_heads: A={A} outside [1, {TD3_MAX_A}]")
+    if mode in (V10_ACT, V10_RANDOM) and (noise_c is None or noise_d is None):
+        raise ValueError("td3v10_heads: noise_c and noise_d [B, A] are needed in this mode")
+    _ba(noise_c, "noise_c", B, A)
+    _ba(noise_d, "noise_d", B, A)
+    _ba(uniform, "uniform", B, A)
+    dev = noise_c.device if pre_c is None else pre_c.device
+    c = torch.empty(B, A, dtype=torch.float32, device=dev)
+    sm = torch.empty(B, A, dtype=torch.float32, device=dev) if want_softmax else None
+    d = torch.empty(B, A, dtype=torch.float32, device=dev) if mode != V10_BEST else None
+    ix = torch.empty(B, 1, dtype=torch.int64, device=dev) if want_index else None
+    lib.ctr_td3v10_heads(B, A, mode, _p(pre_c), _p(pre_d), ldp, _p(noise_c), _p(noise_d),
+                         _p(uniform), float(temperature), _p(c), _p(sm), _p(d), _p(ix), _stream())
+    return dict(c_means=c, c_softmax=sm, d_action=d, d_index=ix)
+
+
+def td3v10_rank_mask(d: torch.Tensor, c: torch.Tensor, *, noise=None, out_c=None, out_d=None,
+                     want_keep: bool = True) -> dict:
+    """The rank mask of the continuous actions under the discrete choice, one launch:
+    dict(c [B, A], keep [B, A] uint8). Row b keeps column m when m is among the top
+    argmax(d[b]) + 1 columns of c by value (ties: the lower index first); a kept element is
+    clamp(c, -1, 1), or clamp(c + (0.2 noise + c), -1, 1) with noise, the others 0. out_c /
+    out_d (one row stride): the c and d column blocks of a critic's input; out_d gets d."""
+    ldd = _ld2(d, "d")
+    B, A = d.shape
+    ldc = _ld2(c, "c")
+    if tuple(c.shape) != (B, A) or not 1 <= A <= TD3_MAX_A:
+        raise ValueError(f"td3v10_rank_mask: d and c must be [B, A] with A in [1, {TD3_MAX_A}]")
+    _ba(noise, "noise", B, A)
+    if out_c is None:
+        out_c = torch.empty(B, A, dtype=torch.float32, device=d.device)
+    ldo = _ld2(out_c, "out_c")
+    if tuple(out_c.shape) != (B, A):
+        raise ValueError(f"td3v10_rank_mask: out_c must be [{B}, {A}]")
+    if out_d is not None and (tuple(out_d.shape) != (B, A) or _ld2(out_d, "out_d") != ldo):
+        raise ValueError(f"td3v10_rank_mask: out_d must be [{B}, {A}] with out_c's row stride")
+    keep = torch.empty(B, A, dtype=torch.uint8, device=d.device) if want_keep else None
+    lib.ctr_td3v10_rank_mask(B, A, _p(d), ldd, _p(c), ldc, _p(noise), _p(out_c), _p(out_d), ldo,
+                             _p(keep), _stream())
+    return dict(c=out_c, keep=keep)
+
+
+def td3v10_heads_backward(g_c: torch.Tensor, g_d: torch.Tensor, keep: torch.Tensor,
+                          c_means: torch.Tensor, d_q: torch.Tensor, d_soft: torch.Tensor,
+                          temperature: float, reg: float):
+    """The actor loss's gradients at the heads' pre-activations (d_pre_c, d_d_q) from the critic
+    input's gradients of the c and d columns (include/ctr_hip.h), one launch."""
+    ldg = _ld2(g_c, "g_c")
+    B, A = g_c.shape
+    if tuple(g_d.shape) != (B, A) or _ld2(g_d, "g_d") != ldg:
+        raise ValueError("td3v10_heads_backward: g_c and g_d must have one shape and row stride")
+    if not 1 <= A <= TD3_MAX_A:
+        raise ValueError(f"td3v10_heads_backward: A={A} outside [1, {TD3_MAX_A}]")
+    ldq = _ld2(d_q, "d_q")
+    _dev(keep, "keep")
+    if keep.dtype != torch.uint8 or tuple(keep.shape) != (B, A) or not keep.is_contiguous():
+        raise ValueError(f"td3v10_heads_backward: keep must be contiguous uint8 [{B}, {A}]")
+    _ba(c_means, "c_means", B, A)
+    _ba(d_soft, "d_soft", B, A)
+    if tuple(d_q.shape) != (B, A):
+        raise ValueError(f"td3v10_heads_backward: d_q must be [{B}, {A}]")
+    out = torch.empty(2, B, A, dtype=torch.float32, device=g_c.device)
+    lib.ctr_td3v10_heads_backward(B, A, _p(g_c), _p(g_d), ldg, _p(keep), _p(c_means), _p(d_q),
+                                  ldq, _p(d_soft), float(temperature), float(reg), _p(out[0]),
+                                  _p(out[1]), _stream())
+    return out[0], out[1]
+
+
+_clip_ws: dict = {}  # (device index, stream, count) -> the partial sums' scratch
+
+
+def clip_grad_norm_(grads, max_norm: float, norm_out: torch.Tensor | None = None) -> torch.Tensor:
+    """torch's clip_grad_norm_ (2-norm) over a list of float32 device tensors in two launches,
+    in place: the fp64 sum of squares in a fixed order, then every element times
+    min(1, max_norm / (norm + 1e-6)). Returns the norm before clipping as a device scalar;
+    nothing is copied to the host or to the device (the table travels as kernel arguments)."""
+    grads = [g for g in grads if g is not None and g.numel()]
+    if not 1 <= len(grads) <= GRAD_CLIP_MAX_TENSORS:
+        raise ValueError(f"clip_grad_norm_: {len(grads)} tensors, outside "
+                         f"[1, {GRAD_CLIP_MAX_TENSORS}]")
+    table = (GradEntry * len(grads))()
+    for i, g in enumerate(grads):
+        _f32(g, "grad")
+        table[i].grad, table[i].numel = g.data_ptr(), g.numel()
+    dev = grads[0].device
+    if any(g.device != dev for g in grads):
+        raise ValueError("clip_grad_norm_: the tensors must be on one device")
+    if norm_out is None:
+        norm_out = torch.empty((), dtype=torch.float32, device=dev)
+    _f32(norm_out, "norm_out")
+    key = (dev.index, _stream(), len(grads))
+    ws = _clip_ws.get(key)
+    if ws is None:
+        ws = _clip_ws[key] = torch.empty(lib.ctr_grad_clip_workspace_bytes(len(grads)),
+                                         dtype=torch.uint8, device=dev)
+    mx = max(g.numel() for g in grads)
+    lib.ctr_grad_sumsq(len(grads), table, mx, _p(ws), ws.numel(), _stream())
+    lib.ctr_grad_clip_scale(len(grads), table, mx, float(max_norm), _p(ws), ws.numel(),
+                            _p(norm_out), _stream())
+    return norm_out
+
+
+def _v10_store_args(memory: torch.Tensor, prio2: torch.Tensor, transitions: torch.Tensor):
+    _f32(memory, "memory")
+    _f32(prio2, "prio2")
+    if memory.dim() != 2 or tuple(prio2.shape) != (memory.shape[0], 2):
+        raise ValueError("td3v10: memory must be [N, T] and prio2 [N, 2]")
+    N, T = memory.shape
+    _dev(transitions, "transitions")
+    if transitions.dtype != torch.float32 or transitions.dim() != 2 or transitions.shape[1] != T:
+        raise ValueError(f"td3v10: transitions must be float32 [n, {T}]")
+    n = transitions.shape[0]
+    if n > N:
+        raise ValueError(f"td3v10: {n} transitions do not fit a memory of {N}")
+    return N, T, n, (_ld2(transitions, "transitions") if n else T)
+
+
+def td3v10_add(memory: torch.Tensor, prio2: torch.Tensor, start: int, transitions: torch.Tensor,
+               td2: torch.Tensor) -> None:
+    """v10 Memory.add: rows to slots (start + i) % N, both priority columns OVERWRITTEN by
+    td2 [n, 2]. One launch."""
+    N, T, n, ldt = _v10_store_args(memory, prio2, transitions)
+    _f32(td2, "td2")
+    if tuple(td2.shape) != (n, 2):
+        raise ValueError(f"td3v10_add: td2 must be [{n}, 2]")
+    lib.ctr_td3v10_store(N, T, start, n, _p(transitions), ldt, _p(td2), None, 0, _p(memory),
+                         _p(prio2), None, _stream())
+
+
+def td3v10_store_seeded(memory: torch.Tensor, prio2: torch.Tensor, start: int,
+                        transitions: torch.Tensor, ws: torch.Tensor,
+                        seed_out: torch.Tensor | None = None) -> None:
+    """v10 store_transition in two launches of one entry point, nothing read back: the max of the WHOLE prio2
+    (both columns, unfilled rows included), then the rows with priorities (1 if that max is 0
+    else the max, the row's reward). ws: >= 4096 bytes of device scratch."""
+    N, T, n, ldt = _v10_store_args(memory, prio2, transitions)
+    _dev(ws, "ws")
+    if ws.dtype != torch.uint8 or not ws.is_contiguous() or ws.numel() < _V10_MAX_WS_BYTES:
+        raise ValueError(f"td3v10_store_seeded: ws must hold {_V10_MAX_WS_BYTES} bytes (uint8)")
+    if seed_out is not None:
+        _f32(seed_out, "seed_out")
+    if n == 0:
+        return
+    lib.ctr_td3v10_store(N, T, start, n, _p(transitions), ldt, None, _p(ws), ws.numel(),
+                         _p(memory), _p(prio2), _p(seed_out), _stream())
+
+
+def _v10_prio2(prio2: torch.Tensor, n_valid: int, who: str) -> int:
+    _f32(prio2, "prio2")
+    if prio2.dim() != 2 or prio2.shape[1] != 2 or not 0 <= n_valid <= prio2.shape[0]:
+        raise ValueError(f"{who}: prio2 must be [N, 2] and n_valid within [0, N]")
+    return prio2.shape[0]
+
+
+def td3v10_keys(prio2: torch.Tensor, n_valid: int, eps: float, alpha: float, seed: int,
+                out: torch.Tensor | None = None) -> torch.Tensor:
+    """The selection keys of rows [0, n_valid) of the v10 memory, bitwise what td3v10_sample
+    orders by: per_keys on (|prio2[:, 0]| + eps)^alpha, evaluated on the fly."""
+    _v10_prio2(prio2, n_valid, "td3v10_keys")
+    if out is None:
+        out = torch.empty(n_valid, dtype=torch.float32, device=prio2.device)
+    _f32(out, "keys")
+    if out.numel() < n_valid:
+        raise ValueError("td3v10_keys: out is shorter than n_valid")
+    lib.ctr_td3v10_keys(n_valid, _p(prio2), float(eps), float(alpha), int(seed) & (2**64 - 1),
+                        _p(out), _stream())
+    return out
+
+
+def td3v10_sample(memory: torch.Tensor, prio2: torch.Tensor, n_valid: int, k: int, seed: int,
+                  beta: float, eps: float, alpha: float) -> dict:
+    """per_sample's stochastic draw on the v10 memory: k distinct rows of the filled prefix by
+    the priorities (|prio2[:, 0]| + eps)^alpha, which are computed where they are read (keys,
+    minimum, isw) and never stored: dict(idx [k] int64, batch [k, T], isw [k, 1], min_p [1])."""
+    _f32(memory, "memory")
+    N = _v10_prio2(prio2, n_valid, "td3v10_sample")
+    if memory.dim() != 2 or memory.shape[0] != N:
+        raise ValueError("td3v10_sample: memory must be [N, T] beside prio2 [N, 2]")
+    T = memory.shape[1]
+    if not 1 <= k <= min(n_valid, PER_MAX_K):
+        raise ValueError(f"td3v10_sample: k={k} outside [1, min(n_valid={n_valid}, {PER_MAX_K})]")
+    dev = memory.device
+    out = dict(idx=torch.empty(k, dtype=torch.int64, device=dev),
+               batch=torch.empty(k, T, dtype=torch.float32, device=dev),
+               isw=torch.empty(k, 1, dtype=torch.float32, device=dev),
+               min_p=torch.empty(1, dtype=torch.float32, device=dev))
+    key = (dev.index, _stream(), N, k)  # the select's scratch, shared with per_sample
+    ws = _per_ws.get(key)
+    if ws is None:
+        ws = _per_ws[key] = torch.empty(lib.ctr_per_workspace_bytes(N, k), dtype=torch.uint8,
+                                        device=dev)
+    lib.ctr_td3v10_sample(N, T, n_valid, k, int(seed) & (2**64 - 1), float(beta), float(eps),
+                          float(alpha), _p(memory), _p(prio2), _p(out["idx"]), _p(out["batch"]),
+                          _p(out["isw"]), _p(out["min_p"]), _p(ws), ws.numel(), _stream())
+    return out
+
+
+def td3v10_update(prio2: torch.Tensor, idx: torch.Tensor, td: torch.Tensor) -> None:
+    """v10 batch_update: prio2[idx, 0] = td, the raw signed error (duplicates: undefined)."""
+    _f32(prio2, "prio2")
+    _dev(idx, "idx")
+    if prio2.dim() != 2 or prio2.shape[1] != 2:
+        raise ValueError("td3v10_update: prio2 must be [N, 2]")
+    if idx.dtype != torch.int64 or idx.dim() != 1 or not idx.is_contiguous():
+        raise ValueError("td3v10_update: idx must be a contiguous int64 vector")
+    _per_td(td, idx.numel())
+    lib.ctr_td3v10_update(prio2.shape[0], idx.numel(), _p(idx), _p(td), _p(prio2), _stream())
+
+
+def bn_eval_backward(dy: torch.Tensor, x: torch.Tensor, running_mean, running_var,
+                     eps: float = 1e-5):
+    """(dgamma, dbeta) of an eval-mode BatchNorm1d from dy, x [B, N] and the running
+    statistics, one launch. The input's gradient is not computed."""
+    lddy = _ld2(dy, "dy")
+    B, N = dy.shape
+    ldx = _ld2(x, "x")
+    if tuple(x.shape) != (B, N):
+        raise ValueError(f"bn_eval_backward: x must be [{B}, {N}]")
+    _vecN(running_mean, "running_mean", N)
+    _vecN(running_var, "running_var", N)
+    out = torch.empty(2, N, dtype=torch.float32, device=dy.device)
+    lib.ctr_bn_eval_backward(B, N, _p(dy), lddy, _p(x), ldx, _p(running_mean), _p(running_var),
+                             float(eps), _p(out[0]), _p(out[1]), _stream())
+    return out[0], out[1]
 
 
 def ensemble_preds(preds: torch.Tensor, actions: torch.Tensor, prob_weights: torch.Tensor,
