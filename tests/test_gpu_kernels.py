@@ -139,6 +139,10 @@ def test_sparse_plan_empty(cuda):
 @pytest.mark.parametrize("S,V", [(1, 1), (15, 3), (16, 1), (17, 1), (1000, 10), (5000, 4000),
                                  (20000, 60)])
 def test_segment_sum_rows(cuda, K, S, V):
+    """Random keys with one hot row, against float64: the sizes (up to 20000 slots), not the
+    path edges — where a row's run starts and ends relative to the chunks, the piece counts
+    around the lane-group and whole-wave thresholds, the float path's idle lanes and the
+    unsupported shapes are placed on purpose in tests/test_gpu_fm_path.py."""
     H = _hip()
     rng = np.random.default_rng(S + K)
     keys = rng.integers(0, V, size=S)
@@ -171,6 +175,10 @@ def test_segment_sum_rows(cuda, K, S, V):
 @pytest.mark.parametrize("K", [10, 16, 64, 128])
 @pytest.mark.parametrize("F", [1, 8, 26, 39, 70])
 def test_fm_forward_vs_oracle(cuda, K, F):
+    """The FM forward against the oracle at B = 67 for four K (K/4 = 4, 16, 32 and the generic
+    kernel). Every other template and dispatch edge (K/4 = 1, 2, 8, 64; F = 32 / 33 and
+    64 / 65; the generic kernel's column loop and fallbacks; B = 1, 4, 5; the optional outputs;
+    fm_forward_planes) is in tests/test_gpu_fm_path.py, which reuses this test's bars."""
     H = _hip()
     V, B = 500, 67
     rng = np.random.default_rng(K * 100 + F)
