@@ -665,6 +665,26 @@ int ctr_ipnn_backward(const void* idx, int idx_type, int64_t B, int F, int K, in
                       const float* emb, const float* dcat, int64_t ldd, float* dslot,
                       ctr_stream_t stream);
 
+/* ------------------------------------------------ OPNN (OuterPNN) ---------------------
+ * p_model.OuterPNN.forward (p_model.py:244-251). With s[b, :] = sum_f E[x_bf, :] (fp32, in
+ * field order) and ksum [K] = kernel.sum(0) of the model's K x K kernel, the reference's
+ * cross term sum_i (s_j * kernel[i,j]) * s_j is ksum[j] * s[b,j]^2 (two rounded products).
+ * ctr_opnn_forward: cat[b] = flat(E[x_b]) (F*K, bit-exact copies) ++ ksum * s^2 (K), written
+ *   as fp32 cat [B, >= F*K + K] (row stride ldc) and / or as its three bf16 planes
+ *   (cat_planes, valid region only) — at least one of the two; sum_e [B, K] (optional) = s,
+ *   which the backward reads. Ids outside [0, V) read row 0 and raise CTR_EFLAG_INDEX.
+ * ctr_opnn_backward: dslot[b*F+f, k] (slot order, [B*F, K]) = dcat[b, f*K+k]
+ *   + ((2*ksum[k]) * s[b,k]) * dcat[b, F*K+k] (product rounded before the sum); reads dcat
+ *   (row stride ldd), sum_e and ksum only. Per-row sums then go through ctr_segment_sum_rows.
+ * Any F >= 1, K >= 1. 16-byte accesses when K % 4 == 0 and the pointers and strides are
+ * 16-byte aligned, scalar ones otherwise: the same result either way. B == 0: no launch. */
+int ctr_opnn_forward(const void* idx, int idx_type, int64_t B, int F, int K, int64_t V,
+                     const float* emb, const float* ksum, float* cat, int64_t ldc,
+                     const ctr_planes* cat_planes, float* sum_e, int32_t* err_flag,
+                     ctr_stream_t stream);
+int ctr_opnn_backward(int64_t B, int F, int K, const float* sum_e, const float* ksum,
+                      const float* dcat, int64_t ldd, float* dslot, ctr_stream_t stream);
+
 /* ------------------------------------------------ DCN: the cross network --------------
  * For B examples with x0 = flat(E[x_b]) [D] (row stride ldx), W and bias [L, D] contiguous
  * (the stacked cross_net_w[i].weight and cross_net_b[i]), 1 <= L <= 8:

@@ -357,6 +357,9 @@ SIGNATURES = {
     "ctr_ipnn_forward_planes": (_i32, [_vp, _i32, _i64, _i32, _i32, _i64, _vp, _vp, _i64,
                                        _planes_p, _vp, _vp]),
     "ctr_ipnn_backward": (_i32, [_vp, _i32, _i64, _i32, _i32, _i64, _vp, _vp, _i64, _vp, _vp]),
+    "ctr_opnn_forward": (_i32, [_vp, _i32, _i64, _i32, _i32, _i64, _vp, _vp, _vp, _i64,
+                                _planes_p, _vp, _vp, _vp]),
+    "ctr_opnn_backward": (_i32, [_i64, _i32, _i32, _vp, _vp, _vp, _i64, _vp, _vp]),
     "ctr_dcn_cross_workspace_bytes": (_i64, [_i64, _i32, _i32]),
     "ctr_dcn_cross_forward": (_i32, [_i64, _i32, _i32, _vp, _i64, _vp, _vp, _vp, _vp, _vp, _i64,
                                      _vp, _vp]),

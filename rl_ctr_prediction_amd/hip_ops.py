@@ -1286,6 +1286,68 @@ def ipnn_backward(idx: torch.Tensor, emb: torch.Tensor, dcat: torch.Tensor,
     return out
 
 
+def opnn_forward(idx: torch.Tensor, emb: torch.Tensor, ksum: torch.Tensor,
+                 out: torch.Tensor | None = None, err_flag=None, planes: "Planes | None" = None,
+                 sum_e: torch.Tensor | None = None) -> torch.Tensor | None:
+    """OuterPNN MLP input [B, F*K + K]: flat embeddings, then ksum * (sum_f e_f)^2 — the
+    reference's kernel-weighted outer-product term, ksum = kernel.sum(0) (p_model.py:244-251).
+    planes: also (or, with out=None, only) written as its three bf16 planes; sum_e [B, K]
+    (optional) receives the field sum the backward reads. Returns out (None when only the
+    planes are written)."""
+    idx, it = _idx(idx)
+    _f32(emb, "feature_embedding.weight")
+    _f32(ksum, "ksum")
+    B, F = idx.shape
+    V, K = emb.shape
+    W = F * K + K
+    if ksum.numel() != K:
+        raise ValueError(f"opnn_forward: ksum must hold K = {K} values, got {ksum.numel()}")
+    if out is not None:
+        _dev(out, "out")
+        if (out.dtype != torch.float32 or out.dim() != 2 or out.shape[0] < B
+                or out.shape[1] < W or out.stride(1) != 1):
+            raise ValueError(f"opnn_forward: out must be float32 [>= {B}, >= {W}], unit "
+                             "column stride")
+    if planes is not None and (planes.rows < B or planes.cols < W):
+        raise ValueError(f"opnn_forward: planes [{planes.rows}, {planes.cols}] < [{B}, {W}]")
+    if sum_e is not None:
+        _f32(sum_e, "sum_e")
+        if sum_e.numel() < B * K:
+            raise ValueError(f"opnn_forward: sum_e must hold [{B}, {K}]")
+    if out is None and planes is None:
+        out = torch.empty(B, W, dtype=torch.float32, device=emb.device)
+    lib.ctr_opnn_forward(_p(idx), it, B, F, K, V, _p(emb), _p(ksum), _p(out),
+                         out.stride(0) if out is not None else 0,
+                         planes.desc if planes is not None else None, _p(sum_e), _p(err_flag),
+                         _stream())
+    return out
+
+
+def opnn_backward(sum_e: torch.Tensor, ksum: torch.Tensor, dcat: torch.Tensor, F: int,
+                  out: torch.Tensor | None = None) -> torch.Tensor:
+    """Per-slot embedding gradients [B*F, K] (slot order) of OuterPNN's MLP input from
+    dL/dcat [B, >= F*K + K], the forward's field sums sum_e [B, K] and ksum [K]."""
+    _f32(sum_e, "sum_e")
+    _f32(ksum, "ksum")
+    _dev(dcat, "dcat")
+    B, K = sum_e.shape
+    F = int(F)
+    if (dcat.dtype != torch.float32 or dcat.dim() != 2 or dcat.shape[0] < B
+            or dcat.shape[1] < F * K + K or dcat.stride(1) != 1):
+        raise ValueError("opnn_backward: dcat must be float32 [B, >= F*K + K], unit column stride")
+    if ksum.numel() != K:
+        raise ValueError(f"opnn_backward: ksum must hold K = {K} values, got {ksum.numel()}")
+    if out is None:
+        out = torch.empty(B * F, K, dtype=torch.float32, device=dcat.device)
+    else:
+        _f32(out, "out")
+        if out.numel() < B * F * K:
+            raise ValueError(f"opnn_backward: out must hold [{B * F}, {K}]")
+    lib.ctr_opnn_backward(B, F, K, _p(sum_e), _p(ksum), _p(dcat), dcat.stride(0), _p(out),
+                          _stream())
+    return out
+
+
 def _rows2d(t: torch.Tensor, name: str, B: int, D: int) -> torch.Tensor:
     """A float32 device matrix with >= B rows of >= D unit-stride columns (rows may be
     strided: a view into a wider buffer)."""

@@ -13,10 +13,10 @@ reference:
     both days' predictions and AUCs are written (``{day}_test_submission.csv``,
     ``day_aucs.csv`` rows [day, auc]) (:206-238);
   * IPNN / FNN / OPNN start from the FM-pretrained embedding
-    ``models/model_params/{campaign}FMbest.pth`` (:164-168; OPNN is out of scope).
+    ``models/model_params/{campaign}FMbest.pth`` (:164-168).
 
 Same flags and defaults as the reference (:256-269). The training step is the fused HIP
-step (FNN and DCN: the reference's own step through autograd over the HIP kernels); batches come in file order from one device-resident copy (the reference's
+step (FM, DeepFM, IPNN, OPNN, FFM; LR, FNN and DCN: the reference's own step through autograd over the HIP kernels); batches come in file order from one device-resident copy (the reference's
 DataLoader without shuffle).
 """
 from __future__ import annotations
@@ -75,7 +75,7 @@ def main(data_path, dataset_name, campaign_id, valid_day, test_day, latent_dims,
     train_data_loader, valid_data_loader, test_data_loader = loaders
 
     model = get_model(model_name, feature_nums, field_nums, latent_dims).to(device)
-    if model_name in ("IPNN", "FNN"):  # main/pretrain_main.py:164-168
+    if model_name in ("IPNN", "OPNN", "FNN"):  # main/pretrain_main.py:164-168
         fm_params = torch.load("models/model_params/" + campaign_id + "FMbest.pth",
                                map_location=device, weights_only=True)
         model.load_embedding(fm_params)
@@ -148,7 +148,7 @@ def _parser():
     parser.add_argument("--valid_day", type=int, default=11, help="6, 7, 8, 9, 10, 11, 12")
     parser.add_argument("--test_day", type=int, default=12, help="6, 7, 8, 9, 10, 11, 12")
     parser.add_argument("--campaign_id", default="1458/", help="1458, 3358, 3386, 3427, 3476")
-    parser.add_argument("--model_name", default="FM", help="LR, FM, FFM, DeepFM, IPNN, FNN, DCN")
+    parser.add_argument("--model_name", default="FM", help="LR, FM, FFM, DeepFM, IPNN, OPNN, FNN, DCN")
     parser.add_argument("--latent_dims", type=int, default=8)
     parser.add_argument("--epoch", type=int, default=100)
     parser.add_argument("--learning_rate", type=float, default=1e-4)

@@ -1,7 +1,7 @@
-"""LR, FM, FFM, DeepFM, InnerPNN, FNN and DCN with the reference's construction API, on the
+"""LR, FM, FFM, DeepFM, InnerPNN, OuterPNN, FNN and DCN with the reference's construction API, on the
 HIP kernels.
 
-Drop-in for ``src/models/p_model.py`` (LR 9-26, FM 28-57, FFM 59-100, InnerPNN 146-200, DeepFM 256-324,
+Drop-in for ``src/models/p_model.py`` (LR 9-26, FM 28-57, FFM 59-100, InnerPNN 146-200, OuterPNN 202-254, DeepFM 256-324,
 FNN 326-373, DCN 376-435): identical constructor
 signatures, submodules created in the same order (so ``torch.manual_seed(s)`` gives the
 same initial weights as the reference) and identical state_dict keys, so the RL drivers'
@@ -141,6 +141,32 @@ class _IPNNPart(torch.autograd.Function):
         grad_rows, _ = hip_ops.segment_sum_rows(plan, dslot)
         g_emb, _ = hip_ops.rows_to_dense(plan, V, grad_rows)
         return None, g_emb
+
+
+class _OPNNPart(torch.autograd.Function):
+    """cat = flat(E[x]) ++ ksum * (sum_f e_f)^2 (p_model.py:244-251). Backward: the per-slot
+    gradients (ctr_opnn_backward, from the saved field sums: no second gather), summed per row
+    in slot order (deterministic), returned dense like embedding_dense_backward."""
+
+    @staticmethod
+    def forward(ctx, x, emb, ksum):
+        B, F = x.shape
+        sum_e = torch.empty(B, emb.shape[1], dtype=torch.float32, device=emb.device)
+        cat = hip_ops.opnn_forward(x, emb, ksum, sum_e=sum_e)
+        # ksum is the model's cache, refreshed in place: the backward needs this call's values
+        ctx.save_for_backward(x, sum_e, ksum.clone())
+        ctx.V = emb.shape[0]
+        return cat
+
+    @staticmethod
+    def backward(ctx, gcat):
+        x, sum_e, ksum = ctx.saved_tensors
+        B, F = x.shape
+        dslot = hip_ops.opnn_backward(sum_e, ksum, gcat.contiguous(), F)
+        plan = hip_ops.SparsePlanBuffers(B * F, gcat.device).build(x, ctx.V)
+        grad_rows, _ = hip_ops.segment_sum_rows(plan, dslot)
+        g_emb, _ = hip_ops.rows_to_dense(plan, ctx.V, grad_rows)
+        return None, g_emb, None
 
 
 class _FFMPart(torch.autograd.Function):
@@ -354,6 +380,77 @@ class InnerPNN(nn.Module):
             return torch.sigmoid(mlp_forward(self.mlp, cat, self.training))
         with torch.no_grad():
             h = hip_ops.ipnn_forward(x, E.detach())
+            m = self.mlp
+            p0 = m[2].p if self.training else 0.0
+            p1 = m[5].p if self.training else 0.0
+            h = hip_ops.linear(h, m[0].weight, m[0].bias, relu=True, drop_p=p0,
+                               seed=_dropout_seed())
+            h = hip_ops.linear(h, m[3].weight, m[3].bias, relu=True, drop_p=p1,
+                               seed=_dropout_seed())
+            zero = torch.zeros(h.shape[0], dtype=torch.float32, device=h.device)
+            head = hip_ops.deepfm_head(h, m[6].weight, m[6].bias, zero)
+            return head["p"].view(-1, 1)
+
+
+class OuterPNN(nn.Module):
+    """p_model.py:202-254: MLP [F*K + K -> 300 -> 200 -> 1] (ReLU, Dropout 0.2) over the flat
+    embeddings and the kernel-weighted outer-product term of their field sum s,
+    sum_i (s_j * kernel[i,j]) * s_j = kernel.sum(0)[j] * s_j^2; no linear term, no bias.
+    ``kernel`` (ones, as in the reference, where it is a plain attribute) is a non-persistent
+    buffer: absent from state_dict, it follows ``.to()``; it is not trained."""
+
+    def __init__(self, feature_nums, field_nums, latent_dims, output_dim=1):
+        super().__init__()
+        latent_dims = int(latent_dims)
+        if output_dim != 1:
+            raise NotImplementedError("OuterPNN: output_dim must be 1 (the reference's only use)")
+        self.feature_nums = feature_nums
+        self.field_nums = field_nums
+        self.latent_dims = latent_dims
+        self.feature_embedding = nn.Embedding(self.feature_nums, self.latent_dims)
+        deep_input_dims = self.latent_dims + self.field_nums * self.latent_dims
+        layers = []
+        for neuron_num in (300, 200):
+            layers.append(nn.Linear(deep_input_dims, neuron_num))
+            layers.append(nn.ReLU())
+            layers.append(nn.Dropout(p=0.2))
+            deep_input_dims = neuron_num
+        layers.append(nn.Linear(deep_input_dims, 1))
+        self.mlp = nn.Sequential(*layers)
+        self.register_buffer("kernel", torch.ones((self.latent_dims, self.latent_dims)),
+                             persistent=False)
+        # kernel.sum(0), what the kernels read: one buffer, refreshed in place (ksum())
+        self.register_buffer("_ksum", torch.zeros(self.latent_dims), persistent=False)
+        self._ksum_key = None
+
+    def ksum(self) -> torch.Tensor:
+        """The cached column sums of ``kernel``, refreshed in place when the kernel was
+        replaced or written (its data pointer or version counter moved). Nothing is read
+        back to the host. Writes through ``kernel.data`` bypass the counter: assign or
+        ``copy_`` instead."""
+        kern = self.kernel
+        if kern.requires_grad:
+            raise NotImplementedError("OuterPNN: the kernel is a constant (as in the reference); "
+                                      "a kernel that requires grad is not supported")
+        K = self.latent_dims
+        if tuple(kern.shape) != (K, K):
+            raise ValueError(f"OuterPNN: kernel must be [{K}, {K}], got {tuple(kern.shape)}")
+        # the tensor itself is held too: a freed kernel's address can be handed out again
+        key = (kern.data_ptr(), kern._version, self._ksum.data_ptr())
+        src = self._ksum_key
+        if src is None or src[0] is not kern or src[1] != key:
+            self._ksum.copy_(kern.detach().sum(0), non_blocking=True)
+            self._ksum_key = (kern, key)
+        return self._ksum
+
+    def forward(self, x):
+        E = self.feature_embedding.weight
+        ksum = self.ksum()
+        if torch.is_grad_enabled() and any(p.requires_grad for p in self.parameters()):
+            cat = _OPNNPart.apply(x, E, ksum)
+            return torch.sigmoid(mlp_forward(self.mlp, cat, self.training))
+        with torch.no_grad():
+            h = hip_ops.opnn_forward(x, E.detach(), ksum)
             m = self.mlp
             p0 = m[2].p if self.training else 0.0
             p1 = m[5].p if self.training else 0.0

@@ -8,10 +8,10 @@ out), same semantics: batches in file order (no shuffle), Adam re-created every 
 AUC over the concatenated test predictions, loss-/AUC-based early stopping with reload
 of the checkpoint four epochs back.
 
-Differences, all deliberate: the training step is the fused HIP step (FM, DeepFM and
-IPNN; FFM: FusedFFMTrainer, the same deferred-exact Adam over its F*V field-table rows;
+Differences, all deliberate: the training step is the fused HIP step (FM, DeepFM, IPNN
+and OPNN; FFM: FusedFFMTrainer, the same deferred-exact Adam over its F*V field-table rows;
 LR, FNN and DCN: AutogradTrainer, the reference's own step — autograd over the HIP kernels and
-torch.optim.Adam — which also serves the other models for comparison; W&D, OPNN and AFM
+torch.optim.Adam — which also serves the other models for comparison; W&D and AFM
 are out of scope); the batches are
 sliced from one device-resident copy of the data instead of 8 DataLoader worker
 processes; the rotating-checkpoint cleanup skips files that were never written (the
@@ -55,6 +55,8 @@ def get_model(model_name, feature_nums, field_nums, latent_dims):
         return Model.DeepFM(feature_nums, field_nums, latent_dims)
     if model_name == "IPNN":
         return Model.InnerPNN(feature_nums, field_nums, latent_dims)
+    if model_name == "OPNN":
+        return Model.OuterPNN(feature_nums, field_nums, latent_dims)
     if model_name == "FFM":
         return Model.FFM(feature_nums, field_nums, latent_dims)
     if model_name == "FNN":
@@ -62,13 +64,14 @@ def get_model(model_name, feature_nums, field_nums, latent_dims):
     if model_name == "DCN":
         return Model.DCN(feature_nums, field_nums, latent_dims)
     raise NotImplementedError(
-        f"{model_name}: LR, FM, FFM, DeepFM, IPNN, FNN and DCN are built on HIP; "
-        "of LR/W&D/OPNN/AFM (SURVEY.md §2 row 7) only LR is built")
+        f"{model_name}: LR, FM, FFM, DeepFM, IPNN, OPNN, FNN and DCN are built on HIP; "
+        "W&D and AFM are not built: of LR/W&D/OPNN/AFM (SURVEY.md §2 row 7) not only LR is "
+        "built but OPNN too")
 
 
 def make_trainer(model_name, model, learning_rate, weight_decay):
     """The training step of a model family: the fused HIP step where one exists (FM, DeepFM,
-    IPNN; FFM), else the reference's own step through autograd (LR, FNN, DCN)."""
+    IPNN, OPNN; FFM), else the reference's own step through autograd (LR, FNN, DCN)."""
     if model_name == "FFM":
         return FusedFFMTrainer(model, lr=learning_rate, weight_decay=weight_decay)
     if model_name in ("LR", "FNN", "DCN"):
@@ -334,7 +337,7 @@ def _parser():
     parser.add_argument("--data_path", default="../../data/")
     parser.add_argument("--dataset_name", default="avazu/", help="ipinyou, cretio, yoyi, avazu")
     parser.add_argument("--campaign_id", default="avazu/", help="1458, 3358, 3386, 3427, 3476, avazu")
-    parser.add_argument("--model_name", default="FM", help="LR, FM, FFM, DeepFM, IPNN, FNN, DCN")
+    parser.add_argument("--model_name", default="FM", help="LR, FM, FFM, DeepFM, IPNN, OPNN, FNN, DCN")
     parser.add_argument("--latent_dims", type=int, default=10)
     parser.add_argument("--epoch", type=int, default=20)
     parser.add_argument("--learning_rate", type=float, default=1e-3)

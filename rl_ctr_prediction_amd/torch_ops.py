@@ -16,6 +16,9 @@ autograd formula and every one with a fake (meta) kernel for shape propagation.
     torch.ops.ctr.ipnn_cat(x, emb) -> [B, F*K + F(F-1)/2]
         InnerPNN's MLP input (p_model.py:187-195). Backward: per-slot gradients, then
         ctr::emb_scatter_add.
+    torch.ops.ctr.opnn_cat(x, emb, ksum) -> [B, F*K + K]
+        OuterPNN's MLP input (p_model.py:244-251), ksum [K] = kernel.sum(0) (a constant: no
+        gradient). Backward: per-slot gradients, then ctr::emb_scatter_add.
     torch.ops.ctr.pairwise_fe(x, emb) -> [B, F(F-1)/2 + F*K]
         Feature_Embedding.forward (Feature_embedding.py:51-59); the reference detaches the
         result, so no autograd formula (pass a detached table, as Feature_Embedding does).
@@ -39,7 +42,7 @@ from torch import Tensor
 
 from . import hip_ops
 
-__all__ = ["fm_fwd", "fm_bwd", "deepfm_gather_concat", "emb_scatter_add", "ipnn_cat",
+__all__ = ["fm_fwd", "fm_bwd", "deepfm_gather_concat", "emb_scatter_add", "ipnn_cat", "opnn_cat",
            "pairwise_fe", "adam_dense", "adam_rowwise", "pg_returns"]
 
 _lib = torch.library
@@ -166,6 +169,36 @@ def _ipnn_backward(ctx, gcat):
 
 
 ipnn_cat.register_autograd(_ipnn_backward, setup_context=_ipnn_setup)
+
+
+# ---------------------------------------------------------------------------- OPNN ----
+@_lib.custom_op("ctr::opnn_cat", mutates_args=())
+def opnn_cat(x: Tensor, emb: Tensor, ksum: Tensor) -> Tensor:
+    return hip_ops.opnn_forward(x, emb, ksum)
+
+
+@opnn_cat.register_fake
+def _(x, emb, ksum):
+    K = emb.shape[1]
+    return _f32(x.shape[0], x.shape[1] * K + K, like=emb)
+
+
+def _opnn_setup(ctx, inputs, output):
+    ctx.save_for_backward(*inputs)
+
+
+def _opnn_backward(ctx, gcat):
+    x, emb, ksum = ctx.saved_tensors
+    B, F = x.shape
+    # the field sums again (the op's only output is cat): the op layer is the drop-in
+    # boundary, the fused trainer keeps them from its forward
+    sum_e = _f32(B, emb.shape[1], like=emb)
+    hip_ops.opnn_forward(x, emb, ksum, sum_e=sum_e)
+    dslot = hip_ops.opnn_backward(sum_e, ksum, gcat.contiguous(), F)
+    return None, torch.ops.ctr.emb_scatter_add(x, dslot, emb.shape[0]), None
+
+
+opnn_cat.register_autograd(_opnn_backward, setup_context=_opnn_setup)
 
 
 # ----------------------------------------------------------- Feature_Embedding (A7) ----

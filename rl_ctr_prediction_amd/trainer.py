@@ -38,7 +38,7 @@ import torch.nn as nn
 from . import hip_ops
 from ._lib import lib
 from .distributed import allgather_sparse_rows, allreduce_sum_, world
-from .p_model import FM, DeepFM, InnerPNN
+from .p_model import FM, DeepFM, InnerPNN, OuterPNN
 
 
 @contextlib.contextmanager
@@ -97,7 +97,9 @@ DEEPFM_DENSE = ("bias", "mlp.0.weight", "mlp.0.bias", "mlp.3.weight", "mlp.3.bia
                 "mlp.6.weight", "mlp.6.bias")
 FM_DENSE = ("bias",)
 IPNN_DENSE = DEEPFM_DENSE[1:]  # InnerPNN: the MLP only (no linear term, no bias)
-_MLP_KINDS = ("DeepFM", "IPNN")
+_MLP_KINDS = ("DeepFM", "IPNN", "OPNN")
+# the product networks: no linear table, per-slot embedding gradients (b.dslot) summed per row
+_PNN_KINDS = ("IPNN", "OPNN")
 
 
 class InputSlot:
@@ -148,8 +150,8 @@ class _Bufs:
     gplan: hip_ops.SparsePlanBuffers | None = None
     g_rows: torch.Tensor | None = None
     g_lin: torch.Tensor | None = None
-    dslot: torch.Tensor | None = None  # IPNN: per-slot embedding gradients [S, K]
-    zero: torch.Tensor | None = None   # IPNN: the (absent) FM logit, zeros [B]
+    dslot: torch.Tensor | None = None  # IPNN / OPNN: per-slot embedding gradients [S, K]
+    zero: torch.Tensor | None = None   # IPNN / OPNN: the (absent) FM logit, zeros [B]
     plan_own: hip_ops.SparsePlanBuffers | None = None  # the shape's plan without lookahead
     xps: dict | None = None  # pipelined tail: X plane buffers by index (_xp_for)
     xp_idx: int = 0
@@ -167,11 +169,12 @@ class FusedCTRTrainer:
     def __init__(self, model: nn.Module, lr: float = 1e-3, weight_decay: float = 0.0,
                  betas=(0.9, 0.999), eps: float = 1e-8, process_group=None, seed: int | None = None,
                  optimizer_mode: str = "deferred"):
-        if not isinstance(model, (FM, DeepFM, InnerPNN)):
-            raise TypeError("FusedCTRTrainer drives FM, DeepFM or InnerPNN")
+        if not isinstance(model, (FM, DeepFM, InnerPNN, OuterPNN)):
+            raise TypeError("FusedCTRTrainer drives FM, DeepFM, InnerPNN or OuterPNN")
         self.model = model
         self.kind = ("DeepFM" if isinstance(model, DeepFM) else
-                     "IPNN" if isinstance(model, InnerPNN) else "FM")
+                     "IPNN" if isinstance(model, InnerPNN) else
+                     "OPNN" if isinstance(model, OuterPNN) else "FM")
         self.lr, self.weight_decay, self.betas, self.eps = float(lr), float(weight_decay), betas, eps
         self.group = process_group
         E = model.feature_embedding.weight
@@ -179,8 +182,10 @@ class FusedCTRTrainer:
         if self.device.type != "cuda":
             raise RuntimeError("FusedCTRTrainer needs the model on a ROCm device")
         self.V, self.K = self._vocab_size(E), E.shape[1]
+        self._ksum_ptr = model.ksum().data_ptr() if self.kind == "OPNN" else None
         named = dict(model.named_parameters())
-        self.dense_names = {"DeepFM": DEEPFM_DENSE, "FM": FM_DENSE, "IPNN": IPNN_DENSE}[self.kind]
+        self.dense_names = {"DeepFM": DEEPFM_DENSE, "FM": FM_DENSE, "IPNN": IPNN_DENSE,
+                            "OPNN": IPNN_DENSE}[self.kind]
         # 16-B aligned views (offsets multiples of 4 floats): the GEMMs read the weights
         # through the float4 / LDS-DMA path only when a row start is 16-B aligned
         self.offsets, total = {}, 0
@@ -211,7 +216,7 @@ class FusedCTRTrainer:
         n_rows = self.E_tab.shape[0]  # V_tab (+ a spare row under row sharding)
         self.m_E = torch.zeros_like(self.E_tab)
         self.v_E = torch.zeros_like(self.E_tab)
-        if self.kind == "IPNN":  # no linear table: every lin pointer of the ABI is NULL
+        if self.kind in _PNN_KINDS:  # no linear table: every lin pointer of the ABI is NULL
             self.w_tab = self.m_w = self.v_w = None
         else:
             self.w_tab = self._own_rows(model.linear.weight.data)
@@ -501,9 +506,10 @@ class FusedCTRTrainer:
         dev, K = self.device, self.K
         e = lambda *s: torch.empty(*s, dtype=torch.float32, device=dev)  # noqa: E731
         deep = self.kind in _MLP_KINDS
-        W = F * K + (F * (F - 1) // 2 if self.kind == "IPNN" else 0)  # MLP input width
+        # MLP input width: IPNN appends the F(F-1)/2 pair products, OPNN the K cross columns
+        W = F * K + {"IPNN": F * (F - 1) // 2, "OPNN": K}.get(self.kind, 0)
         # DeepFM writes its MLP input straight as planes (b.xp): no fp32 copy of X
-        x_fp32 = deep and not (self.kind == "IPNN" or hip_ops.fm_forward_planes_ok(K, F))
+        x_fp32 = deep and not (self.kind in _PNN_KINDS or hip_ops.fm_forward_planes_ok(K, F))
         fm = hip_ops.FMForward(z=e(B), sum_e=e(B, K), emb_out=e(B, W) if x_fp32 else None,
                                p=None, loss_elem=e(B), gz=e(B))
         S = B * F
@@ -523,7 +529,7 @@ class FusedCTRTrainer:
             b.xps = {0: b.xp} if self._pipe else None
             b.h1p = P(B, H1, dev, ones_col=True)
             b.dh2p, b.dh1p = P(B, H2, dev), P(B, H1, dev)
-            if self.kind == "IPNN":
+            if self.kind in _PNN_KINDS:
                 b.dslot = e(S, K)
                 b.zero = torch.zeros(B, dtype=torch.float32, device=dev)
             # dH2 goes to the GEMMs as planes only: no fp32 copy (6.5 MB a step at C3)
@@ -591,6 +597,14 @@ class FusedCTRTrainer:
         B, F = x.shape
         rank, ws = world()
         mean_div = float(global_batch if global_batch is not None else B * ws)
+        if self.kind == "OPNN":
+            # kernel.sum(0), refreshed in place before anything is enqueued or captured: a
+            # replayed graph reads the buffer's current values. The step's launches (and the
+            # captured graphs) hold the buffer's address, like the parameters' views
+            if self.model.ksum().data_ptr() != self._ksum_ptr:
+                raise RuntimeError("FusedCTRTrainer: the OuterPNN's ksum buffer was replaced "
+                                   "(model.to(...) after the trainer was built?); build a new "
+                                   "trainer for the moved model")
         self._sync_weight_planes()
         self._bound_staleness()
         if ws != 1:  # replicated data parallel: eager (the exchange sizes live on the host)
@@ -901,7 +915,7 @@ class FusedCTRTrainer:
         y = y.contiguous()
         m = self.model
         E, bias = m.feature_embedding.weight.data, self.views.get("bias")
-        w = m.linear.weight.data if self.kind != "IPNN" else None
+        w = m.linear.weight.data if self.kind not in _PNN_KINDS else None
         gv = self.grad_views
         step_hint = self.step_count + 1
         self._ev_wplanes = None
@@ -992,7 +1006,7 @@ class FusedCTRTrainer:
         table = (E, self.m_E, self.v_E, w, self.m_w, self.v_w, self.last)
         apply_kw = dict(step_dev=self.step_cur, step_table=self.step_table, step=step_hint,
                         betas=self.betas, eps=self.eps, weight_decay=self.weight_decay)
-        if self.kind == "IPNN":
+        if self.kind in _PNN_KINDS:
             if fused:
                 hip_ops.segment_sum_rows_adam(b.plan, b.dslot, None, table, **apply_kw,
                                               out=b.grad_rows, keep_sums=self.keep_grads)
@@ -1103,6 +1117,11 @@ class FusedCTRTrainer:
         if self.kind == "IPNN":  # cat = flat(E[x]) ++ pairwise inner products, as planes
             X = hip_ops.ipnn_forward(x, E, out=None, err_flag=self.err, planes=b.xp)
             z_fm = b.zero
+        elif self.kind == "OPNN":  # cat = flat(E[x]) ++ ksum * (sum_f e_f)^2, as planes; the
+            # field sums stay in b.fm.sum_e for the backward (one launch writes both)
+            X = hip_ops.opnn_forward(x, E, self.model._ksum, out=None, err_flag=self.err,
+                                     planes=b.xp, sum_e=b.fm.sum_e)
+            z_fm = b.zero
         elif b.fm.emb_out is None:  # gather + FM, the MLP input written as its planes
             hip_ops.fm_forward_planes(x, E, w, bias, b.xp, b.fm.z, b.fm.sum_e, err_flag=self.err)
             X, z_fm = None, b.fm.z
@@ -1138,6 +1157,8 @@ class FusedCTRTrainer:
         self._gemm_planes(b.dh1p, w0p, False, True, B, W, H1, out=b.dx)
         if self.kind == "IPNN":  # per-slot embedding gradients through the pair products
             hip_ops.ipnn_backward(x, E, b.dx, out=b.dslot)
+        elif self.kind == "OPNN":  # per-slot gradients from dX and the saved field sums
+            hip_ops.opnn_backward(b.fm.sum_e, self.model._ksum, b.dx, x.shape[1], out=b.dslot)
         b.ev_dx = torch.cuda.Event()
         b.ev_dx.record()
         return gz
