@@ -713,6 +713,55 @@ int ctr_dcn_cross_backward(int64_t B, int D, int L, const float* x0, int64_t ldx
                            float* dx0, int64_t ldd, float* dW, float* dbias, float* dw_tail,
                            void* ws, int64_t ws_bytes, ctr_stream_t stream);
 
+/* ------------------------------------------------ AFM: pairwise attention -------------
+ * p_model.AFM.forward (p_model.py:472-486) up to the pooled vector. Per example b with
+ * e_f = E[x_bf] [K] and the pairs p = (i, j), i < j, in row-major order, P = F(F-1)/2:
+ *   q_p = e_i * e_j;  h_p = relu(W1 q_p + b1) [A];  s_p = <w2, h_p> + b2[0];
+ *   a = softmax_p(s) (max-subtracted);  a'_p = a_p * m1[b,p];  o = sum_p a'_p q_p;  o' = o * m2[b,k]
+ * W1 [A, K] = attention_net.weight, b1 [A], w2 [A] = attention_softmax.weight, b2 [1].
+ * ctr_afm_forward: pooled [B, K] (row stride ldp) = o'; attn [B, P] (optional) = a, the
+ *   softmax BEFORE dropout, the only activation the backward keeps. Ids outside [0, V) read
+ *   row 0 and raise CTR_EFLAG_INDEX.
+ * ctr_afm_backward: from dpooled = dL/do' [B, K] (row stride ldg) and attn: dslot [B*F, K]
+ *   (slot order; per-row sums then go through ctr_segment_sum_rows) and the batch sums dW1
+ *   [A, K], db1 [A], dw2 [A], db2 [1]. It gathers e again, recomputes h and takes a from attn:
+ *   with do = do' * m2, da_p = m1_p <do, q_p>, c = sum_p a_p da_p, ds_p = a_p (da_p - c),
+ *   dh_p = ds_p * w2 * [h_p > 0] (gradient 0 at 0), dq_p = W1^T dh_p + a'_p do,
+ *   de_i += dq_p * e_j, de_j += dq_p * e_i; dW1 = sum dh_p (x) q_p, db1 = sum dh_p,
+ *   dw2 = sum ds_p h_p, db2 = sum ds_p (zero up to rounding: softmax is shift-invariant).
+ * Contracts:
+ *   - 2 <= F <= 64, 1 <= K <= 128, 1 <= A <= 128, 0 <= drop_p < 1; anything else, a null
+ *     pointer, ldp / ldg < K and a workspace smaller than ctr_afm_workspace_bytes (which does
+ *     not depend on B and is a multiple of 16) return CTR_ERR_INVALID before any HIP call.
+ *   - B == 0: the forward launches nothing, the backward zero-fills the four batch sums.
+ *   - Nothing of size B*P*K or B*P*A reaches global memory: a block stages its example's F
+ *     rows once in LDS and forms the pair products from them.
+ *   - Any K and A. 16-byte accesses where K and the pointers allow (the gather, W1 in the
+ *     backward, dslot), scalar ones otherwise: the same result either way. The K x A product
+ *     is plain fp32 FMA.
+ *   - Deterministic, no float atomics: a slot's F-1 contributions are added in a fixed
+ *     pair order (the rounds of a round-robin schedule); the batch sums are per-block partials in row order in ws, added in block
+ *     order by a second launch; two calls on the same inputs give the same bits. Without
+ *     dropout (whose counters hold b) a row's pooled, attn and dslot do not depend on B or on
+ *     the row's position.
+ *   - Dropout: mask element = hash_u32(seed, ctr) >= drop_p*2^32 ? 1/(1-drop_p) : 0 with the
+ *     threshold and scale of ctr_gemm_f32 (formed in double from the fp32 drop_p, the
+ *     threshold clamped to 2^32 - 1 and truncated); ctr = b*(P+K) + p for m1 and
+ *     b*(P+K) + P + k for m2 (uint64). The backward recomputes both from (seed, drop_p).
+ *     drop_p == 0: no hash is evaluated.
+ * Replaces: p_model.py:473-482 and autograd through them. */
+int64_t ctr_afm_workspace_bytes(int64_t B, int F, int K, int A);
+int ctr_afm_forward(const void* idx, int idx_type, int64_t B, int F, int K, int A, int64_t V,
+                    const float* emb, const float* W1, const float* b1, const float* w2,
+                    const float* b2, float drop_p, uint64_t seed, float* pooled, int64_t ldp,
+                    float* attn, int32_t* err_flag, ctr_stream_t stream);
+int ctr_afm_backward(const void* idx, int idx_type, int64_t B, int F, int K, int A, int64_t V,
+                     const float* emb, const float* W1, const float* b1, const float* w2,
+                     const float* b2, float drop_p, uint64_t seed, const float* attn,
+                     const float* dpooled, int64_t ldg, float* dslot, float* dW1, float* db1,
+                     float* dw2, float* db2, void* ws, int64_t ws_bytes, int32_t* err_flag,
+                     ctr_stream_t stream);
+
 /* ------------------------------------- Prioritized replay memory (hybrid TD3, PER) ------
  * The reference's Memory (Hybrid_TD3_model_PER.py:22-109) with storage and sampling on the
  * device: memory [N, T] and prio [N] (the [N, 1] priority column) are fp32, contiguous, and
@@ -1241,6 +1290,24 @@ typedef struct ctr_bn_eval_backward_args {
   const float* running_mean; const float* running_var; float eps; float* dgamma; float* dbeta;
 } ctr_bn_eval_backward_args;
 int ctr_op_bn_eval_backward(const ctr_bn_eval_backward_args* a, ctr_stream_t stream);
+
+/* ctr::afm_pool — ctr_afm_forward / ctr_afm_backward with their arguments in a struct (the
+ * flat entry points' contract; ws sized by ctr_afm_workspace_bytes). */
+typedef struct ctr_afm_fwd_args {
+  const void* idx; int idx_type; int64_t B; int F; int K; int A; int64_t V;
+  const float* emb; const float* W1; const float* b1; const float* w2; const float* b2;
+  float drop_p; uint64_t seed; float* pooled; int64_t ldp; float* attn; int32_t* err_flag;
+} ctr_afm_fwd_args;
+int ctr_op_afm_fwd(const ctr_afm_fwd_args* a, ctr_stream_t stream);
+
+typedef struct ctr_afm_bwd_args {
+  const void* idx; int idx_type; int64_t B; int F; int K; int A; int64_t V;
+  const float* emb; const float* W1; const float* b1; const float* w2; const float* b2;
+  float drop_p; uint64_t seed; const float* attn; const float* dpooled; int64_t ldg;
+  float* dslot; float* dW1; float* db1; float* dw2; float* db2;
+  void* ws; int64_t ws_bytes; int32_t* err_flag;
+} ctr_afm_bwd_args;
+int ctr_op_afm_bwd(const ctr_afm_bwd_args* a, ctr_stream_t stream);
 
 #ifdef __cplusplus
 }

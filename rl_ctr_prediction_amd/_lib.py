@@ -229,6 +229,21 @@ class BnEvalBackwardArgs(C.Structure):
                 ("dbeta", _vp)]
 
 
+_AFMF = [("idx", _vp), ("idx_type", _i32), ("B", _i64), ("F", _i32), ("K", _i32), ("A", _i32),
+         ("V", _i64), ("emb", _vp), ("W1", _vp), ("b1", _vp), ("w2", _vp), ("b2", _vp),
+         ("drop_p", _f32), ("seed", _u64)]
+
+
+class AfmFwdArgs(C.Structure):
+    _fields_ = _AFMF + [("pooled", _vp), ("ldp", _i64), ("attn", _vp), ("err_flag", _vp)]
+
+
+class AfmBwdArgs(C.Structure):
+    _fields_ = _AFMF + [("attn", _vp), ("dpooled", _vp), ("ldg", _i64), ("dslot", _vp),
+                        ("dW1", _vp), ("db1", _vp), ("dw2", _vp), ("db2", _vp), ("ws", _vp),
+                        ("ws_bytes", _i64), ("err_flag", _vp)]
+
+
 CTR_GRAD_CLIP_MAX_TENSORS = 64
 CTR_TD3V10_MAX_WS_BYTES = 4096
 
@@ -243,7 +258,8 @@ OP_ARGS = {"fm_fwd": FmFwdArgs, "fm_bwd": FmBwdArgs, "deepfm_gather_concat": Dee
            "td3v10_heads_backward": Td3v10HeadsBackwardArgs, "grad_sumsq": GradSumsqArgs,
            "grad_clip_scale": GradClipScaleArgs, "td3v10_store": Td3v10StoreArgs,
            "td3v10_keys": Td3v10KeysArgs, "td3v10_sample": Td3v10SampleArgs,
-           "td3v10_update": Td3v10UpdateArgs, "bn_eval_backward": BnEvalBackwardArgs}
+           "td3v10_update": Td3v10UpdateArgs, "bn_eval_backward": BnEvalBackwardArgs,
+           "afm_fwd": AfmFwdArgs, "afm_bwd": AfmBwdArgs}
 
 
 # name -> (restype, argtypes); the list is the whole ABI and tests/test_abi.py checks it
@@ -360,6 +376,12 @@ SIGNATURES = {
     "ctr_opnn_forward": (_i32, [_vp, _i32, _i64, _i32, _i32, _i64, _vp, _vp, _vp, _i64,
                                 _planes_p, _vp, _vp, _vp]),
     "ctr_opnn_backward": (_i32, [_i64, _i32, _i32, _vp, _vp, _vp, _i64, _vp, _vp]),
+    "ctr_afm_workspace_bytes": (_i64, [_i64, _i32, _i32, _i32]),
+    "ctr_afm_forward": (_i32, [_vp, _i32, _i64, _i32, _i32, _i32, _i64, _vp, _vp, _vp, _vp, _vp,
+                               _f32, _u64, _vp, _i64, _vp, _vp, _vp]),
+    "ctr_afm_backward": (_i32, [_vp, _i32, _i64, _i32, _i32, _i32, _i64, _vp, _vp, _vp, _vp, _vp,
+                                _f32, _u64, _vp, _vp, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _i64,
+                                _vp, _vp]),
     "ctr_dcn_cross_workspace_bytes": (_i64, [_i64, _i32, _i32]),
     "ctr_dcn_cross_forward": (_i32, [_i64, _i32, _i32, _vp, _i64, _vp, _vp, _vp, _vp, _vp, _i64,
                                      _vp, _vp]),

@@ -231,6 +231,21 @@ extern "C" int ctr_op_pairwise_fe(const ctr_pairwise_fe_args* a, ctr_stream_t st
                                        a->out, a->err_flag, stream);
 }
 
+extern "C" int ctr_op_afm_fwd(const ctr_afm_fwd_args* a, ctr_stream_t stream) {
+  CTR_REQUIRE(a, "ctr_op_afm_fwd: null args");
+  return ctr_afm_forward(a->idx, a->idx_type, a->B, a->F, a->K, a->A, a->V, a->emb, a->W1, a->b1,
+                         a->w2, a->b2, a->drop_p, a->seed, a->pooled, a->ldp, a->attn,
+                         a->err_flag, stream);
+}
+
+extern "C" int ctr_op_afm_bwd(const ctr_afm_bwd_args* a, ctr_stream_t stream) {
+  CTR_REQUIRE(a, "ctr_op_afm_bwd: null args");
+  return ctr_afm_backward(a->idx, a->idx_type, a->B, a->F, a->K, a->A, a->V, a->emb, a->W1,
+                          a->b1, a->w2, a->b2, a->drop_p, a->seed, a->attn, a->dpooled, a->ldg,
+                          a->dslot, a->dW1, a->db1, a->dw2, a->db2, a->ws, a->ws_bytes,
+                          a->err_flag, stream);
+}
+
 extern "C" int ctr_op_pg_returns(const ctr_pg_returns_args* a, ctr_stream_t stream) {
   CTR_REQUIRE(a, "ctr_op_pg_returns: null args");
   CTR_REQUIRE(a->n >= 0, "ctr_op_pg_returns: bad size");

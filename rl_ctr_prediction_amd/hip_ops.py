@@ -24,7 +24,8 @@ __all__ = [
     "tensor_sum", "colsum", "transpose", "Planes", "split_planes", "gemm_planes", "SparsePlanBuffers", "fm_embedding_grad", "segment_sum_rows",
     "fm_embedding_grad_adam", "segment_sum_rows_adam",
     "rows_to_dense", "adam_dense", "fm_step_tail", "adam_embedding", "adam_scalars", "feature_embedding",
-    "dcn_cross_forward", "dcn_cross_backward",
+    "dcn_cross_forward", "dcn_cross_backward", "afm_forward", "afm_backward",
+    "AFM_BWD_MAX_BLOCKS",
     "lr_forward", "ensemble_preds", "ensemble_preds_ex", "per_store_step",
     "per_add", "per_update", "per_keys", "per_sample", "PER_STOCHASTIC", "PER_GREEDY", "PER_MAX_K",
     "metrics_workspace_bytes", "metrics_reset", "metrics_append", "metrics_auc", "METRICS_TILE",
@@ -1345,6 +1346,85 @@ def opnn_backward(sum_e: torch.Tensor, ksum: torch.Tensor, dcat: torch.Tensor, F
             raise ValueError(f"opnn_backward: out must hold [{B * F}, {K}]")
     lib.ctr_opnn_backward(B, F, K, _p(sum_e), _p(ksum), _p(dcat), dcat.stride(0), _p(out),
                           _stream())
+    return out
+
+
+AFM_BWD_MAX_BLOCKS = 1024  # csrc/afm.hip kAfmMaxBlocks: the backward's grid and partial slabs
+
+
+def _afm_params(W1, b1, w2, b2, K):
+    for t, name in ((W1, "W1"), (b1, "b1"), (w2, "w2"), (b2, "b2")):
+        _f32(t, name)
+    if W1.dim() != 2 or W1.shape[1] != K:
+        raise ValueError(f"afm: W1 must be [A, {K}], got {tuple(W1.shape)}")
+    A = W1.shape[0]
+    if b1.numel() != A or w2.numel() != A or b2.numel() != 1:
+        raise ValueError(f"afm: b1 and w2 must hold A = {A} values and b2 one")
+    return A
+
+
+def afm_forward(idx: torch.Tensor, emb: torch.Tensor, W1: torch.Tensor, b1: torch.Tensor,
+                w2: torch.Tensor, b2: torch.Tensor, drop_p: float = 0.0, seed: int = 0,
+                want_attn: bool = True, out: torch.Tensor | None = None,
+                attn: torch.Tensor | None = None, err_flag=None):
+    """AFM's attention pooling (p_model.py:473-482): (pooled [B, K], attn [B, F(F-1)/2] or
+    None). attn is the softmax over the pairs before dropout, what afm_backward reads. Both
+    dropouts (attention weights and pooled vector) use one (seed, drop_p); drop_p = 0: none.
+    out: a float32 [>= B, >= K] matrix with unit column stride (rows may be strided)."""
+    idx, it = _idx(idx)
+    _f32(emb, "feature_embedding.weight")
+    B, F = idx.shape
+    V, K = emb.shape
+    A = _afm_params(W1, b1, w2, b2, K)
+    P = F * (F - 1) // 2
+    if out is None:
+        out = torch.empty(B, K, dtype=torch.float32, device=emb.device)
+    else:
+        _rows2d(out, "out", B, K)
+    if attn is None and want_attn:
+        attn = torch.empty(B, P, dtype=torch.float32, device=emb.device)
+    if attn is not None:
+        _f32(attn, "attn")
+        if attn.numel() < B * P:
+            raise ValueError(f"afm_forward: attn must hold [{B}, {P}]")
+    lib.ctr_afm_forward(_p(idx), it, B, F, K, A, V, _p(emb), _p(W1), _p(b1), _p(w2), _p(b2),
+                        float(drop_p), int(seed) & (2**64 - 1), _p(out),
+                        out.stride(0) if B > 1 else K,  # a lone row's stride is arbitrary
+                        _p(attn), _p(err_flag), _stream())
+    return (out if out.shape == (B, K) else out[:B, :K]), attn
+
+
+def afm_backward(idx: torch.Tensor, emb: torch.Tensor, W1: torch.Tensor, b1: torch.Tensor,
+                 w2: torch.Tensor, b2: torch.Tensor, attn: torch.Tensor, dpooled: torch.Tensor,
+                 drop_p: float = 0.0, seed: int = 0, out: dict | None = None,
+                 err_flag=None) -> dict:
+    """Backward of afm_forward from dL/dpooled [B, K] and the forward's attn: dict(dslot
+    [B*F, K] in slot order, dW1 [A, K], db1 [A], dw2 [A], db2 [1]); (seed, drop_p) as in the
+    forward. One kernel over the batch plus the deterministic reduction of its per-block
+    partials."""
+    idx, it = _idx(idx)
+    _f32(emb, "feature_embedding.weight")
+    B, F = idx.shape
+    V, K = emb.shape
+    A = _afm_params(W1, b1, w2, b2, K)
+    P = F * (F - 1) // 2
+    _f32(attn, "attn")
+    if attn.numel() < B * P:
+        raise ValueError(f"afm_backward: attn must hold [{B}, {P}]")
+    _rows2d(dpooled, "dpooled", B, K)
+    if out is None:
+        e = lambda *sh: torch.empty(*sh, dtype=torch.float32, device=emb.device)  # noqa: E731
+        out = dict(dslot=e(B * F, K), dW1=e(A, K), db1=e(A), dw2=e(A), db2=e(1))
+    for name, n in (("dslot", B * F * K), ("dW1", A * K), ("db1", A), ("dw2", A), ("db2", 1)):
+        _f32(out[name], name)
+        if out[name].numel() < n:
+            raise ValueError(f"afm_backward: {name} must hold {n} values")
+    ws = Workspace.get(lib.ctr_afm_workspace_bytes(B, F, K, A), emb.device)
+    lib.ctr_afm_backward(_p(idx), it, B, F, K, A, V, _p(emb), _p(W1), _p(b1), _p(w2), _p(b2),
+                         float(drop_p), int(seed) & (2**64 - 1), _p(attn), _p(dpooled),
+                         dpooled.stride(0) if B > 1 else K,
+                         _p(out["dslot"]), _p(out["dW1"]), _p(out["db1"]), _p(out["dw2"]),
+                         _p(out["db2"]), _p(ws), ws.numel(), _p(err_flag), _stream())
     return out
 
 

@@ -1,8 +1,8 @@
-"""LR, FM, FFM, DeepFM, InnerPNN, OuterPNN, FNN and DCN with the reference's construction API, on the
+"""LR, FM, FFM, DeepFM, InnerPNN, OuterPNN, FNN, DCN and AFM with the reference's construction API, on the
 HIP kernels.
 
 Drop-in for ``src/models/p_model.py`` (LR 9-26, FM 28-57, FFM 59-100, InnerPNN 146-200, OuterPNN 202-254, DeepFM 256-324,
-FNN 326-373, DCN 376-435): identical constructor
+FNN 326-373, DCN 376-435, AFM 438-486): identical constructor
 signatures, submodules created in the same order (so ``torch.manual_seed(s)`` gives the
 same initial weights as the reference) and identical state_dict keys, so the RL drivers'
 ``torch.load('...FMbest.pth')`` / ``load_state_dict`` and ``Feature_Embedding.load_embedding``
@@ -240,6 +240,32 @@ class _CrossPart(torch.autograd.Function):
         return r["dx0"], r["dW"], r["dbias"], r["dw_tail"]
 
 
+class _AFMPart(torch.autograd.Function):
+    """pooled [B, K] = AFM's attention pooling of the pair products (p_model.py:473-482) on
+    ctr_afm_forward; keeps the softmax [B, P] alone. Backward = one ctr_afm_backward (the
+    attention parameters' gradients and the per-slot embedding gradients), the slots summed
+    per row in slot order (deterministic), returned dense like embedding_dense_backward."""
+
+    @staticmethod
+    def forward(ctx, x, emb, W1, b1, w2, b2, drop_p, seed):
+        pooled, attn = hip_ops.afm_forward(x, emb, W1, b1, w2.reshape(-1), b2, drop_p, seed)
+        ctx.save_for_backward(x, emb, W1, b1, w2, b2, attn)
+        ctx.drop = (drop_p, seed)
+        return pooled
+
+    @staticmethod
+    def backward(ctx, gpooled):
+        x, emb, W1, b1, w2, b2, attn = ctx.saved_tensors
+        B, F = x.shape
+        V, K = emb.shape
+        r = hip_ops.afm_backward(x, emb, W1, b1, w2.reshape(-1), b2, attn, gpooled.contiguous(),
+                                 *ctx.drop)
+        plan = hip_ops.SparsePlanBuffers(B * F, emb.device).build(x, V)
+        grad_rows, _ = hip_ops.segment_sum_rows(plan, r["dslot"])
+        g_emb, _ = hip_ops.rows_to_dense(plan, V, grad_rows)
+        return None, g_emb, r["dW1"], r["db1"], r["dw2"].view_as(w2), r["db2"], None, None
+
+
 def _fm_part(x, emb, lin, bias, want_emb):
     return _FMPart.apply(x, emb, lin, bias, want_emb)
 
@@ -460,6 +486,65 @@ class OuterPNN(nn.Module):
                                seed=_dropout_seed())
             zero = torch.zeros(h.shape[0], dtype=torch.float32, device=h.device)
             head = hip_ops.deepfm_head(h, m[6].weight, m[6].bias, zero)
+            return head["p"].view(-1, 1)
+
+
+class AFM(nn.Module):
+    """p_model.py:438-486, the attentional factorisation machine: the pair products
+    e_i * e_j (i < j) go through attention_net (K -> K, ReLU) and attention_softmax (K -> 1), a
+    softmax over the pairs weighs them, and z = bias + sum_f w[x_f] + fc(pooled). Submodules
+    are created in the reference's order, so a seed gives its initial weights and its
+    state_dict keys. The pooling and its backward are one HIP kernel each (ctr_afm_*): no
+    [B, P, K] tensor is formed.
+
+    ``drop_p`` (0.2, the reference's constant) drives both dropouts: on the attention weights
+    and on the pooled vector, with one seed per forward drawn from torch's generator.
+    Deliberate difference: the reference calls ``F.dropout(x, p=0.2)``, whose ``training``
+    flag defaults to True, so it keeps dropping in ``eval()`` and its test predictions are
+    random; here ``eval()`` applies neither dropout."""
+
+    def __init__(self, feature_nums, field_nums, latent_dims, output_dim=1):
+        super().__init__()
+        latent_dims = int(latent_dims)
+        if output_dim != 1:
+            raise NotImplementedError("AFM: output_dim must be 1 (the reference's only use)")
+        if field_nums < 2:
+            raise NotImplementedError("AFM: field_nums must be at least 2 (there is no pair to "
+                                      "attend over otherwise)")
+        self.feature_nums = feature_nums
+        self.field_nums = field_nums
+        self.latent_dims = latent_dims
+        self.feature_embedding = nn.Embedding(self.feature_nums, self.latent_dims)
+        # the reference's pair lists (p_model.py:451-454), kept for API parity
+        self.row, self.col = [], []
+        for i in range(self.field_nums - 1):
+            for j in range(i + 1, self.field_nums):
+                self.row.append(i), self.col.append(j)
+        attention_factor = self.latent_dims
+        self.attention_net = nn.Linear(self.latent_dims, attention_factor)
+        self.attention_softmax = nn.Linear(attention_factor, 1)
+        self.fc = nn.Linear(self.latent_dims, output_dim)
+        self.linear = nn.Embedding(self.feature_nums, output_dim)
+        self.bias = nn.Parameter(torch.zeros((output_dim,)))
+        self.drop_p = 0.2
+
+    def forward(self, x):
+        E = self.feature_embedding.weight
+        an, asm = self.attention_net, self.attention_softmax
+        drop = float(self.drop_p) if self.training else 0.0
+        seed = _rng_dropout_seed() if drop > 0.0 else 0
+        if torch.is_grad_enabled() and any(p.requires_grad for p in self.parameters()):
+            pooled = _AFMPart.apply(x, E, an.weight, an.bias, asm.weight, asm.bias, drop, seed)
+            z = _LRPart.apply(x, self.linear.weight, self.bias) + _LinearAct.apply(
+                pooled, self.fc.weight, self.fc.bias, False, 0.0, 0)
+            return torch.sigmoid(z)
+        with torch.no_grad():
+            pooled, _ = hip_ops.afm_forward(x, E.detach(), an.weight.detach(), an.bias.detach(),
+                                            asm.weight.detach().reshape(-1), asm.bias.detach(),
+                                            drop, seed, want_attn=False)
+            z_lr = hip_ops.lr_forward(x, self.linear.weight.detach(), self.bias.detach(),
+                                      want_p=False)["z"]
+            head = hip_ops.deepfm_head(pooled, self.fc.weight.detach(), self.fc.bias.detach(), z_lr)
             return head["p"].view(-1, 1)
 
 

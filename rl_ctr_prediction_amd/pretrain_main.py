@@ -71,10 +71,10 @@ def get_model(model_name, feature_nums, field_nums, latent_dims):
 
 def make_trainer(model_name, model, learning_rate, weight_decay):
     """The training step of a model family: the fused HIP step where one exists (FM, DeepFM,
-    IPNN, OPNN; FFM), else the reference's own step through autograd (LR, FNN, DCN)."""
+    IPNN, OPNN; FFM), else the reference's own step through autograd (LR, FNN, DCN, AFM)."""
     if model_name == "FFM":
         return FusedFFMTrainer(model, lr=learning_rate, weight_decay=weight_decay)
-    if model_name in ("LR", "FNN", "DCN"):
+    if model_name in ("LR", "FNN", "DCN", "AFM"):
         return AutogradTrainer(model, lr=learning_rate, weight_decay=weight_decay)
     return FusedCTRTrainer(model, lr=learning_rate, weight_decay=weight_decay)
 

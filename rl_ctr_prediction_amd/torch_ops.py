@@ -19,6 +19,10 @@ autograd formula and every one with a fake (meta) kernel for shape propagation.
     torch.ops.ctr.opnn_cat(x, emb, ksum) -> [B, F*K + K]
         OuterPNN's MLP input (p_model.py:244-251), ksum [K] = kernel.sum(0) (a constant: no
         gradient). Backward: per-slot gradients, then ctr::emb_scatter_add.
+    torch.ops.ctr.afm_pool(x, emb, W1, b1, w2, b2) -> pooled [B, K]
+        AFM's attention pooling of the pair products (p_model.py:473-482) without dropout; W1,
+        b1 = attention_net, w2, b2 = attention_softmax. Backward: ctr_afm_backward (the four
+        attention gradients and the per-slot gradients), then ctr::emb_scatter_add.
     torch.ops.ctr.pairwise_fe(x, emb) -> [B, F(F-1)/2 + F*K]
         Feature_Embedding.forward (Feature_embedding.py:51-59); the reference detaches the
         result, so no autograd formula (pass a detached table, as Feature_Embedding does).
@@ -43,7 +47,7 @@ from torch import Tensor
 from . import hip_ops
 
 __all__ = ["fm_fwd", "fm_bwd", "deepfm_gather_concat", "emb_scatter_add", "ipnn_cat", "opnn_cat",
-           "pairwise_fe", "adam_dense", "adam_rowwise", "pg_returns"]
+           "afm_pool", "pairwise_fe", "adam_dense", "adam_rowwise", "pg_returns"]
 
 _lib = torch.library
 
@@ -199,6 +203,35 @@ def _opnn_backward(ctx, gcat):
 
 
 opnn_cat.register_autograd(_opnn_backward, setup_context=_opnn_setup)
+
+
+# ----------------------------------------------------------------------------- AFM ----
+@_lib.custom_op("ctr::afm_pool", mutates_args=())
+def afm_pool(x: Tensor, emb: Tensor, W1: Tensor, b1: Tensor, w2: Tensor, b2: Tensor) -> Tensor:
+    return hip_ops.afm_forward(x, emb, W1, b1, w2.reshape(-1), b2, want_attn=False)[0]
+
+
+@afm_pool.register_fake
+def _(x, emb, W1, b1, w2, b2):
+    return _f32(x.shape[0], emb.shape[1], like=emb)
+
+
+def _afm_setup(ctx, inputs, output):
+    ctx.save_for_backward(*inputs)
+
+
+def _afm_backward(ctx, gpooled):
+    x, emb, W1, b1, w2, b2 = ctx.saved_tensors
+    w2f = w2.reshape(-1)
+    # the attention weights again (the op's only output is pooled): the op layer is the
+    # drop-in boundary, p_model._AFMPart keeps them from its forward
+    _, attn = hip_ops.afm_forward(x, emb, W1, b1, w2f, b2)
+    r = hip_ops.afm_backward(x, emb, W1, b1, w2f, b2, attn, gpooled.contiguous())
+    g_emb = torch.ops.ctr.emb_scatter_add(x, r["dslot"], emb.shape[0])
+    return None, g_emb, r["dW1"], r["db1"].view_as(b1), r["dw2"].view_as(w2), r["db2"].view_as(b2)
+
+
+afm_pool.register_autograd(_afm_backward, setup_context=_afm_setup)
 
 
 # ----------------------------------------------------------- Feature_Embedding (A7) ----
