@@ -544,6 +544,39 @@ int ctr_segment_sum_rows_adam(const ctr_sparse_plan* plan, int K, const float* v
                               float* out_lin, int keep_sums, void* ws, int64_t ws_bytes,
                               ctr_stream_t stream);
 
+/* ------------------------------------------------ W&D (WideAndDeep) -------------------
+ * p_model.WideAndDeep.forward (p_model.py:135-144): DeepFM without the second-order term,
+ *   p = sigmoid((bias + sum_f lin[x_f]) + mlp(flat(embedding[x]))).
+ * ctr_wd_forward: one launch writes the MLP input flat(E[x_b]) (F*K, bit-exact copies) as
+ *   fp32 flat [B, >= F*K] (row stride ldf) and / or as its three bf16 planes (x_planes, valid
+ *   region only: padding and a ones column stay as they are) — at least one of the two — and
+ *   z_lin[b] = bias[0] + (lin[x_b0] + lin[x_b1] + ... in field order). No field sum, nothing
+ *   else of size B*K. Any F >= 1, K >= 1 (16-byte accesses when K % 4 == 0 and the pointers
+ *   and strides are 16-byte aligned, scalar ones otherwise: the same result either way); a
+ *   row's outputs depend on that row alone. Ids outside [0, V) read row 0 and raise
+ *   CTR_EFLAG_INDEX. B == 0: no launch.
+ * ctr_wd_embedding_grad (slot s = b*F + f, the segmented sums above with their tree):
+ *     grad_rows[u,:] = sum_{s in row u} dx[s,:]      (dx: the MLP input gradient [B, F*K])
+ *     grad_lin[u]    = sum_{s in row u} gz[b]
+ *   — ctr_segment_sum_rows over vals = dx, vals_lin = gz repeated F times, bit for bit;
+ *   reads neither sum_e nor the table. rowmap as ctr_fm_embedding_grad's.
+ * ctr_wd_embedding_grad_adam: the same sums with the deferred Adam apply fused in, as
+ *   ctr_fm_embedding_grad_adam (K % 4 == 0, K <= 256, 16-byte aligned buffers; the linear
+ *   table is required). ws: ctr_segment_workspace_bytes(S, K). */
+int ctr_wd_forward(const void* idx, int idx_type, int64_t B, int F, int K, int64_t V,
+                   const float* emb, const float* lin, const float* bias, float* flat,
+                   int64_t ldf, const ctr_planes* x_planes, float* z_lin, int32_t* err_flag,
+                   ctr_stream_t stream);
+int ctr_wd_embedding_grad(const ctr_sparse_plan* plan, int F, int K, const float* gz,
+                          const float* dx, float* grad_rows, float* grad_lin, int32_t* rowmap,
+                          void* ws, int64_t ws_bytes, ctr_stream_t stream);
+int ctr_wd_embedding_grad_adam(const ctr_sparse_plan* plan, int F, int K, const float* gz,
+                               const float* dx, const ctr_deferred_table* table,
+                               const int32_t* step_ptr, const float* step_table, double beta1,
+                               double beta2, double eps, double weight_decay, float* grad_rows,
+                               float* grad_lin, int keep_sums, void* ws, int64_t ws_bytes,
+                               ctr_stream_t stream);
+
 /* Device step counters (int32[2]): ctr[0] = completed steps, ctr[1] = the step in flight.
  * ctr_step_begin: ctr[1] = ctr[0] + 1;  ctr_step_end: ctr[0] = ctr[1], ctr[1] += 1. A
  * counter initialised to {0, 1} therefore needs no ctr_step_begin (one launch less per
@@ -1308,6 +1341,30 @@ typedef struct ctr_afm_bwd_args {
   void* ws; int64_t ws_bytes; int32_t* err_flag;
 } ctr_afm_bwd_args;
 int ctr_op_afm_bwd(const ctr_afm_bwd_args* a, ctr_stream_t stream);
+
+/* Wide&Deep — ctr_wd_forward / ctr_wd_embedding_grad / ctr_wd_embedding_grad_adam with their
+ * arguments in a struct (the flat entry points' contract; ws sized by
+ * ctr_segment_workspace_bytes). */
+typedef struct ctr_wd_fwd_args {
+  const void* idx; int idx_type; int64_t B; int F; int K; int64_t V;
+  const float* emb; const float* lin; const float* bias;
+  float* flat; int64_t ldf; const ctr_planes* x_planes; float* z_lin; int32_t* err_flag;
+} ctr_wd_fwd_args;
+int ctr_op_wd_fwd(const ctr_wd_fwd_args* a, ctr_stream_t stream);
+
+typedef struct ctr_wd_embedding_grad_args {
+  const ctr_sparse_plan* plan; int F; int K; const float* gz; const float* dx;
+  float* grad_rows; float* grad_lin; int32_t* rowmap; void* ws; int64_t ws_bytes;
+} ctr_wd_embedding_grad_args;
+int ctr_op_wd_embedding_grad(const ctr_wd_embedding_grad_args* a, ctr_stream_t stream);
+
+typedef struct ctr_wd_embedding_grad_adam_args {
+  const ctr_sparse_plan* plan; int F; int K; const float* gz; const float* dx;
+  const ctr_deferred_table* table; const int32_t* step_ptr; const float* step_table;
+  double beta1; double beta2; double eps; double weight_decay;
+  float* grad_rows; float* grad_lin; int keep_sums; void* ws; int64_t ws_bytes;
+} ctr_wd_embedding_grad_adam_args;
+int ctr_op_wd_embedding_grad_adam(const ctr_wd_embedding_grad_adam_args* a, ctr_stream_t stream);
 
 #ifdef __cplusplus
 }

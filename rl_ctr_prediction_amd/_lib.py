@@ -244,6 +244,26 @@ class AfmBwdArgs(C.Structure):
                         ("ws_bytes", _i64), ("err_flag", _vp)]
 
 
+class WdFwdArgs(C.Structure):
+    _fields_ = _IDXF + [("emb", _vp), ("lin", _vp), ("bias", _vp), ("flat", _vp), ("ldf", _i64),
+                        ("x_planes", _planes_p), ("z_lin", _vp), ("err_flag", _vp)]
+
+
+_WDG = [("plan", _plan_p), ("F", _i32), ("K", _i32), ("gz", _vp), ("dx", _vp)]
+
+
+class WdEmbeddingGradArgs(C.Structure):
+    _fields_ = _WDG + [("grad_rows", _vp), ("grad_lin", _vp), ("rowmap", _vp), ("ws", _vp),
+                       ("ws_bytes", _i64)]
+
+
+class WdEmbeddingGradAdamArgs(C.Structure):
+    _fields_ = _WDG + [("table", _table_p), ("step_ptr", _vp), ("step_table", _vp),
+                       ("beta1", _f64), ("beta2", _f64), ("eps", _f64), ("weight_decay", _f64),
+                       ("grad_rows", _vp), ("grad_lin", _vp), ("keep_sums", _i32), ("ws", _vp),
+                       ("ws_bytes", _i64)]
+
+
 CTR_GRAD_CLIP_MAX_TENSORS = 64
 CTR_TD3V10_MAX_WS_BYTES = 4096
 
@@ -259,7 +279,9 @@ OP_ARGS = {"fm_fwd": FmFwdArgs, "fm_bwd": FmBwdArgs, "deepfm_gather_concat": Dee
            "grad_clip_scale": GradClipScaleArgs, "td3v10_store": Td3v10StoreArgs,
            "td3v10_keys": Td3v10KeysArgs, "td3v10_sample": Td3v10SampleArgs,
            "td3v10_update": Td3v10UpdateArgs, "bn_eval_backward": BnEvalBackwardArgs,
-           "afm_fwd": AfmFwdArgs, "afm_bwd": AfmBwdArgs}
+           "afm_fwd": AfmFwdArgs, "afm_bwd": AfmBwdArgs, "wd_fwd": WdFwdArgs,
+           "wd_embedding_grad": WdEmbeddingGradArgs,
+           "wd_embedding_grad_adam": WdEmbeddingGradAdamArgs}
 
 
 # name -> (restype, argtypes); the list is the whole ABI and tests/test_abi.py checks it
@@ -339,6 +361,13 @@ SIGNATURES = {
                                           _f64, _f64, _f64, _f64, _vp, _vp, _i32, _vp, _i64, _vp]),
     "ctr_segment_sum_rows_adam": (_i32, [_plan_p, _i32, _vp, _vp, _table_p, _vp, _vp, _f64, _f64,
                                          _f64, _f64, _vp, _vp, _i32, _vp, _i64, _vp]),
+    "ctr_wd_forward": (_i32, [_vp, _i32, _i64, _i32, _i32, _i64, _vp, _vp, _vp, _vp, _i64,
+                              _planes_p, _vp, _vp, _vp]),
+    "ctr_wd_embedding_grad": (_i32, [_plan_p, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _i64,
+                                     _vp]),
+    "ctr_wd_embedding_grad_adam": (_i32, [_plan_p, _i32, _i32, _vp, _vp, _table_p, _vp, _vp,
+                                          _f64, _f64, _f64, _f64, _vp, _vp, _i32, _vp, _i64,
+                                          _vp]),
     "ctr_adam_dense_planes": (_i32, [_vp, _vp, _vp, _vp, _i64, _f64, _f64, _vp, _vp, _f64, _f64,
                                      _f64, _f64, _vp, _i32, _vp]),
     "ctr_adam_embedding": (_i32, [_vp, _vp, _vp, _vp, _vp, _vp, _i64, _i32, _vp, _vp, _vp, _f64,

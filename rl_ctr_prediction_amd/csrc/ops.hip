@@ -246,6 +246,28 @@ extern "C" int ctr_op_afm_bwd(const ctr_afm_bwd_args* a, ctr_stream_t stream) {
                           a->err_flag, stream);
 }
 
+extern "C" int ctr_op_wd_fwd(const ctr_wd_fwd_args* a, ctr_stream_t stream) {
+  CTR_REQUIRE(a, "ctr_op_wd_fwd: null args");
+  return ctr_wd_forward(a->idx, a->idx_type, a->B, a->F, a->K, a->V, a->emb, a->lin, a->bias,
+                        a->flat, a->ldf, a->x_planes, a->z_lin, a->err_flag, stream);
+}
+
+extern "C" int ctr_op_wd_embedding_grad(const ctr_wd_embedding_grad_args* a,
+                                        ctr_stream_t stream) {
+  CTR_REQUIRE(a, "ctr_op_wd_embedding_grad: null args");
+  return ctr_wd_embedding_grad(a->plan, a->F, a->K, a->gz, a->dx, a->grad_rows, a->grad_lin,
+                               a->rowmap, a->ws, a->ws_bytes, stream);
+}
+
+extern "C" int ctr_op_wd_embedding_grad_adam(const ctr_wd_embedding_grad_adam_args* a,
+                                             ctr_stream_t stream) {
+  CTR_REQUIRE(a, "ctr_op_wd_embedding_grad_adam: null args");
+  return ctr_wd_embedding_grad_adam(a->plan, a->F, a->K, a->gz, a->dx, a->table, a->step_ptr,
+                                    a->step_table, a->beta1, a->beta2, a->eps, a->weight_decay,
+                                    a->grad_rows, a->grad_lin, a->keep_sums, a->ws, a->ws_bytes,
+                                    stream);
+}
+
 extern "C" int ctr_op_pg_returns(const ctr_pg_returns_args* a, ctr_stream_t stream) {
   CTR_REQUIRE(a, "ctr_op_pg_returns: null args");
   CTR_REQUIRE(a->n >= 0, "ctr_op_pg_returns: bad size");

@@ -163,7 +163,9 @@ __device__ __forceinline__ void seg_final(const SegArgs& a, int64_t u, int c, bo
   seg_emit<VT>(a, u, c, col, acc, accl);
 }
 
-enum { MODE_FM = 0, MODE_VALS = 1 };
+// MODE_WD (Wide&Deep: DeepFM without the second-order term): a slot's value is its slice of
+// dX and its linear gradient its example's gz — no sum_e, no table row, no row term.
+enum { MODE_FM = 0, MODE_VALS = 1, MODE_WD = 2 };
 
 template <typename VT, int LPR, int MODE>
 __global__ __launch_bounds__(256) void seg_chunk_kernel(SegArgs a) {
@@ -204,6 +206,9 @@ __global__ __launch_bounds__(256) void seg_chunk_kernel(SegArgs a) {
             val[i] = VOps<VT>::fm(g, s, e, d);
           }
         }
+      } else if (MODE == MODE_WD) {
+        gl[i] = a.gz[slot / a.F];
+        if (col) val[i] = static_cast<const VT*>(a.dx)[(int64_t)slot * a.KV + c];
       } else {
         if (a.vals_lin) gl[i] = a.vals_lin[slot];
         if (col) val[i] = static_cast<const VT*>(a.vals)[(int64_t)slot * a.KV + c];
@@ -408,6 +413,8 @@ static int launch_seg_lpr(SegArgs& a, int mode, hipStream_t st) {
   const unsigned g1 = (unsigned)ceil_div(n_chunks, groups_per_block);
   if (mode == MODE_FM)
     hipLaunchKernelGGL((seg_chunk_kernel<VT, LPR, MODE_FM>), g1, 256, 0, st, a);
+  else if (mode == MODE_WD)
+    hipLaunchKernelGGL((seg_chunk_kernel<VT, LPR, MODE_WD>), g1, 256, 0, st, a);
   else
     hipLaunchKernelGGL((seg_chunk_kernel<VT, LPR, MODE_VALS>), g1, 256, 0, st, a);
   CTR_LAUNCH_CHECK("seg_chunk_kernel");
@@ -626,6 +633,63 @@ extern "C" int ctr_segment_sum_rows(const ctr_sparse_plan* plan, int K, const fl
   a.vals_lin = vals_lin;
   const bool al = ((uintptr_t)vals | (uintptr_t)out | (uintptr_t)ws) % 16 == 0;
   return launch_seg(a, K, MODE_VALS, as_stream(stream), al);
+}
+
+// Wide&Deep (reference p_model.py:103-144): slot s = b*F + f contributes dx[s, :] to its
+// row's embedding gradient and gz[b] to its linear gradient — the MODE_VALS sums over
+// vals = dx [S, K], vals_lin = gz repeated F times, bit for bit, without that repeat.
+static int wd_grad_args(const char* who, const ctr_sparse_plan* plan, int F, int K,
+                        const float* gz, const float* dx, float* grad_rows, float* grad_lin) {
+  CTR_REQUIRE(plan_ok(plan), "%s: incomplete plan", who);
+  CTR_REQUIRE(F > 0 && K > 0, "%s: bad sizes F=%d K=%d", who, F, K);
+  CTR_REQUIRE(plan->S % F == 0, "%s: the plan's %lld slots are no multiple of F=%d", who,
+              (long long)plan->S, F);
+  CTR_REQUIRE(gz && dx, "%s: null gz / dx", who);
+  CTR_REQUIRE(plan->S == 0 || (grad_rows && grad_lin), "%s: grad_rows / grad_lin needed", who);
+  return CTR_OK;
+}
+
+extern "C" int ctr_wd_embedding_grad(const ctr_sparse_plan* plan, int F, int K, const float* gz,
+                                     const float* dx, float* grad_rows, float* grad_lin,
+                                     int32_t* rowmap, void* ws, int64_t ws_bytes,
+                                     ctr_stream_t stream) {
+  int rc = wd_grad_args("ctr_wd_embedding_grad", plan, F, K, gz, dx, grad_rows, grad_lin);
+  if (rc != CTR_OK) return rc;
+  if (plan->S == 0) return CTR_OK;
+  SegArgs a;
+  rc = seg_prepare(a, plan, K, grad_rows, grad_lin, rowmap, ws, ws_bytes);
+  if (rc != CTR_OK) return rc;
+  a.F = F;
+  a.gz = gz;
+  a.dx = dx;
+  const bool al = ((uintptr_t)dx | (uintptr_t)grad_rows | (uintptr_t)ws) % 16 == 0;
+  return launch_seg(a, K, MODE_WD, as_stream(stream), al);
+}
+
+extern "C" int ctr_wd_embedding_grad_adam(const ctr_sparse_plan* plan, int F, int K,
+                                          const float* gz, const float* dx,
+                                          const ctr_deferred_table* table,
+                                          const int32_t* step_ptr, const float* step_table,
+                                          double beta1, double beta2, double eps,
+                                          double weight_decay, float* grad_rows,
+                                          float* grad_lin, int keep_sums, void* ws,
+                                          int64_t ws_bytes, ctr_stream_t stream) {
+  int rc = wd_grad_args("ctr_wd_embedding_grad_adam", plan, F, K, gz, dx, grad_rows, grad_lin);
+  if (rc != CTR_OK) return rc;
+  if (plan->S == 0) return CTR_OK;
+  SegArgs a;
+  rc = seg_prepare(a, plan, K, grad_rows, grad_lin, nullptr, ws, ws_bytes);
+  if (rc != CTR_OK) return rc;
+  rc = seg_set_apply(a, K, table, step_ptr, step_table, beta1, beta2, eps, weight_decay);
+  if (rc != CTR_OK) return rc;
+  CTR_REQUIRE(table->lin, "ctr_wd_embedding_grad_adam: the linear table is needed");
+  a.out_keep = keep_sums != 0;
+  a.F = F;
+  a.gz = gz;
+  a.dx = dx;
+  CTR_REQUIRE(((uintptr_t)dx | (uintptr_t)grad_rows | (uintptr_t)ws) % 16 == 0,
+              "ctr_wd_embedding_grad_adam: 16-B aligned buffers required");
+  return launch_seg(a, K, MODE_WD, as_stream(stream), true);
 }
 
 extern "C" int ctr_shard_row_grads(const ctr_sparse_plan* plan, int F, int K, const float* emb,

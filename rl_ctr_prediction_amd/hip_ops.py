@@ -25,6 +25,7 @@ __all__ = [
     "fm_embedding_grad_adam", "segment_sum_rows_adam",
     "rows_to_dense", "adam_dense", "fm_step_tail", "adam_embedding", "adam_scalars", "feature_embedding",
     "dcn_cross_forward", "dcn_cross_backward", "afm_forward", "afm_backward",
+    "wd_forward", "wd_embedding_grad", "wd_embedding_grad_adam",
     "AFM_BWD_MAX_BLOCKS",
     "lr_forward", "ensemble_preds", "ensemble_preds_ex", "per_store_step",
     "per_add", "per_update", "per_keys", "per_sample", "PER_STOCHASTIC", "PER_GREEDY", "PER_MAX_K",
@@ -1350,6 +1351,95 @@ def opnn_backward(sum_e: torch.Tensor, ksum: torch.Tensor, dcat: torch.Tensor, F
 
 
 AFM_BWD_MAX_BLOCKS = 1024  # csrc/afm.hip kAfmMaxBlocks: the backward's grid and partial slabs
+
+
+def wd_forward(idx: torch.Tensor, emb: torch.Tensor, lin: torch.Tensor, bias: torch.Tensor,
+               out: torch.Tensor | None = None, err_flag=None, planes: "Planes | None" = None,
+               z_lin: torch.Tensor | None = None) -> tuple[torch.Tensor, torch.Tensor | None]:
+    """Wide&Deep's input (p_model.py:140-142) in one launch: z_lin [B] = bias + sum_f lin[x_f]
+    and the MLP input flat(E[x]) [B, F*K], as fp32 (out) and / or as its three bf16 planes
+    (planes; with out=None, the planes only). Returns (z_lin, out); out is None when only the
+    planes are written."""
+    idx, it = _idx(idx)
+    if idx.dim() != 2:
+        raise ValueError("wd_forward: idx must be [B, F]")
+    _f32(emb, "embedding.weight")
+    _f32(lin, "linear.weight")
+    _f32(bias, "bias")
+    B, F = idx.shape
+    V, K = emb.shape
+    W = F * K
+    if lin.numel() != V or bias.numel() != 1:
+        raise ValueError(f"wd_forward: linear.weight must hold V = {V} values and bias one")
+    if out is not None:
+        _dev(out, "out")
+        if (out.dtype != torch.float32 or out.dim() != 2 or out.shape[0] < B
+                or out.shape[1] < W or out.stride(1) != 1):
+            raise ValueError(f"wd_forward: out must be float32 [>= {B}, >= {W}], unit column "
+                             "stride")
+    if planes is not None and (planes.rows < B or planes.cols < W):
+        raise ValueError(f"wd_forward: planes [{planes.rows}, {planes.cols}] < [{B}, {W}]")
+    if z_lin is None:
+        z_lin = torch.empty(B, dtype=torch.float32, device=emb.device)
+    elif _f32(z_lin, "z_lin").numel() < B:
+        raise ValueError(f"wd_forward: z_lin must hold {B} values")
+    if out is None and planes is None:
+        out = torch.empty(B, W, dtype=torch.float32, device=emb.device)
+    lib.ctr_wd_forward(_p(idx), it, B, F, K, V, _p(emb), _p(lin), _p(bias), _p(out),
+                       out.stride(0) if out is not None else 0,
+                       planes.desc if planes is not None else None, _p(z_lin), _p(err_flag),
+                       _stream())
+    return z_lin, out
+
+
+def _wd_grad_inputs(who: str, plan: SparsePlanBuffers, F: int, K: int, gz, dx) -> None:
+    if int(F) < 1 or plan.S % int(F):
+        raise ValueError(f"{who}: the plan's {plan.S} slots must be B * F, F = {F}")
+    if _f32(gz, "gz").numel() < plan.S // int(F):
+        raise ValueError(f"{who}: gz must hold B = {plan.S // int(F)} values")
+    if _f32(dx, "dx").numel() < plan.S * K:
+        raise ValueError(f"{who}: dx must be [{plan.S}, {K}]")
+
+
+def wd_embedding_grad(plan: SparsePlanBuffers, F: int, K: int, gz, dx, rowmap=None,
+                      grad_rows=None, grad_lin=None):
+    """Wide&Deep's per-unique-row gradient sums (ctr_wd_embedding_grad): a slot's embedding
+    gradient is its slice of dx [B, F*K], its linear gradient its example's gz — bitwise
+    segment_sum_rows(plan, dx.view(B*F, K), vals_lin=gz.repeat_interleave(F))."""
+    _wd_grad_inputs("wd_embedding_grad", plan, F, K, gz, dx)
+    cap = max(plan.capacity, 1)
+    if grad_rows is None:
+        grad_rows = torch.empty(cap, K, dtype=torch.float32, device=dx.device)
+    if grad_lin is None:
+        grad_lin = torch.empty(cap, dtype=torch.float32, device=dx.device)
+    ws = _seg_ws(plan, K)
+    lib.ctr_wd_embedding_grad(plan.struct(), int(F), int(K), _p(gz), _p(dx), _p(grad_rows),
+                              _p(grad_lin), _p(rowmap), _p(ws), ws.numel(), _stream())
+    return grad_rows, grad_lin
+
+
+def wd_embedding_grad_adam(plan: SparsePlanBuffers, F: int, gz, dx, table, step_dev,
+                           step_table: "AdamStepTable", step: int, betas=(0.9, 0.999), eps=1e-8,
+                           weight_decay=0.0, grad_rows=None, grad_lin=None,
+                           keep_sums: bool = False) -> None:
+    """wd_embedding_grad + adam_deferred_rows(sums, step = *step_dev) with the apply fused
+    into the combine pass (ctr_wd_embedding_grad_adam): table = (E, m_E, v_E, w, m_w, v_w,
+    last); grad_rows / grad_lin are scratch, holding every row's sum with keep_sums."""
+    dtab = _deferred_table(*table)
+    V, K = table[0].shape
+    _i32(step_dev, "step_dev", 1)
+    _wd_grad_inputs("wd_embedding_grad_adam", plan, F, K, gz, dx)
+    if table[3] is None:
+        raise ValueError("wd_embedding_grad_adam: the linear table is needed")
+    if grad_lin is None:
+        raise ValueError("wd_embedding_grad_adam: grad_rows and grad_lin are needed")
+    _plan_grads(plan, V, K, grad_rows, grad_lin, table[3])
+    ws = _seg_ws(plan, K)
+    tab = step_table.ensure(step)
+    lib.ctr_wd_embedding_grad_adam(plan.struct(), int(F), int(K), _p(gz), _p(dx), dtab,
+                                   _p(step_dev), _p(tab), float(betas[0]), float(betas[1]),
+                                   float(eps), float(weight_decay), _p(grad_rows),
+                                   _p(grad_lin), int(keep_sums), _p(ws), ws.numel(), _stream())
 
 
 def _afm_params(W1, b1, w2, b2, K):

@@ -26,9 +26,9 @@ Differences, all deliberate:
     its loss as a tensor, so an epoch of ``train``, and ``test`` and ``submission``, wait for
     the device once, at the final ``compute()``;
   * ``--ensemble_models`` (default ``LR,FM,FFM``, the reference's set, line 294): any names
-    ``pretrain_main.get_model`` builds, loaded from ``{save_param_dir}{campaign_id}{name}best.pth``
-    and put in ``.eval()`` — the reference's commented-out five-model set minus W&D and AFM is
-    selectable. The state encoder takes its table from ``FMbest.pth`` as in the reference;
+    ``pretrain_main.build_model`` builds, loaded from ``{save_param_dir}{campaign_id}{name}best.pth``
+    and put in ``.eval()`` — the reference's commented-out five-model set (W&D and AFM
+    included) is selectable. The state encoder takes its table from ``FMbest.pth`` as in the reference;
   * ids above 2^24: the replay memory stores the ids as fp32 and ``learn`` reads them back with
     ``.long()``, so above 2^24 an id silently becomes another row (latent in the reference);
     ``main`` raises ``ValueError`` when ``feature_nums - 1 > 2**24``;
@@ -212,10 +212,10 @@ def submission(rl_model, model_dict, embedding_layer, data_loader, device, metri
 def load_ensemble(names, feature_nums, field_nums, latent_dims, save_param_dir, campaign_id,
                   device):
     """({0: model, ...} in the order of `names`, {name: state_dict}): every frozen model built by
-    pretrain_main.get_model, loaded from {save_param_dir}{campaign_id}{name}best.pth, .eval()."""
+    pretrain_main.build_model, loaded from {save_param_dir}{campaign_id}{name}best.pth, .eval()."""
     model_dict, params = {}, {}
     for i, name in enumerate(names):
-        model = _pm.get_model(name, feature_nums, field_nums, latent_dims)
+        model = _pm.build_model(name, feature_nums, field_nums, latent_dims)
         path = save_param_dir + campaign_id + name + "best.pth"
         params[name] = torch.load(path, map_location="cpu", weights_only=True)
         model.load_state_dict(params[name])
@@ -341,7 +341,8 @@ def _parser():
     parser.add_argument("--metrics", default="host", choices=["host", "device"],
                         help="where AUC, validation loss and rewards are computed")
     parser.add_argument("--ensemble_models", default="LR,FM,FFM",
-                        help="comma-separated names pretrain_main.get_model builds")
+                        help="comma-separated names pretrain_main.build_model builds: LR, FM, "
+                             "FFM, W&D, DeepFM, IPNN, OPNN, FNN, DCN, AFM")
     return parser
 
 

@@ -16,7 +16,7 @@ reference:
     ``models/model_params/{campaign}FMbest.pth`` (:164-168).
 
 Same flags and defaults as the reference (:256-269). The training step is the fused HIP
-step (FM, DeepFM, IPNN, OPNN, FFM; LR, FNN and DCN: the reference's own step through autograd over the HIP kernels); batches come in file order from one device-resident copy (the reference's
+step (FM, DeepFM, W&D, IPNN, OPNN, FFM; LR, FNN, DCN and AFM: the reference's own step through autograd over the HIP kernels); batches come in file order from one device-resident copy (the reference's
 DataLoader without shuffle).
 """
 from __future__ import annotations
@@ -31,10 +31,11 @@ import torch
 import torch.nn as nn
 
 from .. import creat_data as Data
+from .. import pretrain_main as _pm
 from ..pretrain_main import (DeviceBatches, eva_stopping, get_model, make_trainer, setup_seed,
                              submission, test, train)
 
-__all__ = ["setup_seed", "get_model", "get_dataset", "train", "test", "submission", "main",
+__all__ = ["setup_seed", "get_model", "build_model", "get_dataset", "train", "test", "submission", "main",
            "eva_stopping"]
 
 
@@ -60,6 +61,12 @@ def get_dataset(datapath, dataset_name, campaign_id, valid_day, test_day):
             feature_nums)
 
 
+def build_model(model_name, feature_nums, field_nums, latent_dims):
+    """pretrain_main.build_model (W&D and AFM besides get_model's families) over this
+    module's get_model, looked up when called."""
+    return _pm.build_model(model_name, feature_nums, field_nums, latent_dims, fallback=get_model)
+
+
 def main(data_path, dataset_name, campaign_id, valid_day, test_day, latent_dims, model_name, epoch,
          learning_rate, weight_decay, early_stop_type, batch_size, device, save_param_dir,
          verbose=True, metrics="host"):
@@ -74,7 +81,7 @@ def main(data_path, dataset_name, campaign_id, valid_day, test_day, latent_dims,
                for d in (train_data, valid_data, test_data)]
     train_data_loader, valid_data_loader, test_data_loader = loaders
 
-    model = get_model(model_name, feature_nums, field_nums, latent_dims).to(device)
+    model = build_model(model_name, feature_nums, field_nums, latent_dims).to(device)
     if model_name in ("IPNN", "OPNN", "FNN"):  # main/pretrain_main.py:164-168
         fm_params = torch.load("models/model_params/" + campaign_id + "FMbest.pth",
                                map_location=device, weights_only=True)
@@ -109,7 +116,7 @@ def main(data_path, dataset_name, campaign_id, valid_day, test_day, latent_dims,
     end_time = datetime.datetime.now()
 
     if is_early_stop:
-        test_model = get_model(model_name, feature_nums, field_nums, latent_dims).to(device)
+        test_model = build_model(model_name, feature_nums, field_nums, latent_dims).to(device)
         load_path = save_param_dir + campaign_id + model_name + str(early_stop_index) + ".pth"
         test_model.load_state_dict(torch.load(load_path, map_location=device, weights_only=True))
     else:
@@ -148,7 +155,7 @@ def _parser():
     parser.add_argument("--valid_day", type=int, default=11, help="6, 7, 8, 9, 10, 11, 12")
     parser.add_argument("--test_day", type=int, default=12, help="6, 7, 8, 9, 10, 11, 12")
     parser.add_argument("--campaign_id", default="1458/", help="1458, 3358, 3386, 3427, 3476")
-    parser.add_argument("--model_name", default="FM", help="LR, FM, FFM, DeepFM, IPNN, OPNN, FNN, DCN")
+    parser.add_argument("--model_name", default="FM", help="LR, FM, FFM, W&D, DeepFM, IPNN, OPNN, FNN, DCN, AFM")
     parser.add_argument("--latent_dims", type=int, default=8)
     parser.add_argument("--epoch", type=int, default=100)
     parser.add_argument("--learning_rate", type=float, default=1e-4)

@@ -1,7 +1,7 @@
-"""LR, FM, FFM, DeepFM, InnerPNN, OuterPNN, FNN, DCN and AFM with the reference's construction API, on the
+"""LR, FM, FFM, WideAndDeep, DeepFM, InnerPNN, OuterPNN, FNN, DCN and AFM with the reference's construction API, on the
 HIP kernels.
 
-Drop-in for ``src/models/p_model.py`` (LR 9-26, FM 28-57, FFM 59-100, InnerPNN 146-200, OuterPNN 202-254, DeepFM 256-324,
+Drop-in for ``src/models/p_model.py`` (LR 9-26, FM 28-57, FFM 59-100, WideAndDeep 103-144, InnerPNN 146-200, OuterPNN 202-254, DeepFM 256-324,
 FNN 326-373, DCN 376-435, AFM 438-486): identical constructor
 signatures, submodules created in the same order (so ``torch.manual_seed(s)`` gives the
 same initial weights as the reference) and identical state_dict keys, so the RL drivers'
@@ -68,6 +68,39 @@ class _FMPart(torch.autograd.Function):
         g_bias = hip_ops.tensor_sum(gz) if ctx.needs_input_grad[3] else None
         return (None, g_emb if ctx.needs_input_grad[1] else None,
                 g_lin if ctx.needs_input_grad[2] else None, g_bias, None)
+
+
+class _WDPart(torch.autograd.Function):
+    """(z_lin [B,1], flat embeddings [B,F*K]) = the wide logit and the MLP input of
+    p_model.py:140-142 in one launch (ctr_wd_forward). Backward: a slot's embedding gradient
+    is its slice of the MLP-input gradient, its linear gradient its example's gz
+    (ctr_wd_embedding_grad), summed per row in slot order (deterministic), returned as dense
+    grads like embedding_dense_backward."""
+
+    @staticmethod
+    def forward(ctx, x, emb, lin, bias):
+        B, F = x.shape
+        z_lin, flat = hip_ops.wd_forward(x, emb, lin, bias)
+        ctx.save_for_backward(x)
+        ctx.VK = tuple(emb.shape)
+        return z_lin.view(B, 1), flat
+
+    @staticmethod
+    def backward(ctx, gz, gflat):
+        (x,) = ctx.saved_tensors
+        B, F = x.shape
+        V, K = ctx.VK
+        dev = x.device
+        gz = (torch.zeros(B, dtype=torch.float32, device=dev) if gz is None
+              else gz.reshape(-1).contiguous())
+        dx = (torch.zeros(B, F * K, dtype=torch.float32, device=dev) if gflat is None
+              else gflat.contiguous())
+        plan = hip_ops.SparsePlanBuffers(B * F, dev).build(x, V)
+        grad_rows, grad_lin = hip_ops.wd_embedding_grad(plan, F, K, gz, dx)
+        g_emb, g_lin = hip_ops.rows_to_dense(plan, V, grad_rows, grad_lin)
+        g_bias = hip_ops.tensor_sum(gz).view(1) if ctx.needs_input_grad[3] else None
+        return (None, g_emb if ctx.needs_input_grad[1] else None,
+                g_lin if ctx.needs_input_grad[2] else None, g_bias)
 
 
 class _LRPart(torch.autograd.Function):
@@ -328,6 +361,52 @@ class FM(nn.Module):
         r = hip_ops.fm_forward(x, self.feature_embedding.weight.detach(),
                                self.linear.weight.detach(), self.bias.detach(), want_sum=False)
         return r.p.view(-1, 1)
+
+
+class WideAndDeep(nn.Module):
+    """p_model.py:103-144: z = (bias + sum_f w[x_f]) + MLP [F*K -> 300 -> 200 -> 1] (ReLU,
+    Dropout 0.2) over the flat embeddings — DeepFM without the second-order term. The table
+    is ``embedding`` (not ``feature_embedding``), as in the reference."""
+
+    def __init__(self, feature_nums, field_nums, latent_dims, output_dim=1):
+        super().__init__()
+        latent_dims = int(latent_dims)
+        if output_dim != 1:
+            raise NotImplementedError("WideAndDeep: output_dim must be 1 (the reference's only "
+                                      "use)")
+        self.feature_nums = feature_nums
+        self.field_nums = field_nums
+        self.latent_dims = latent_dims
+        self.linear = nn.Embedding(self.feature_nums, output_dim)
+        self.bias = nn.Parameter(torch.zeros((output_dim,)))
+        self.embedding = nn.Embedding(self.feature_nums, self.latent_dims)
+        deep_input_dims = self.field_nums * self.latent_dims
+        layers = []
+        for neuron_num in (300, 200):
+            layers.append(nn.Linear(deep_input_dims, neuron_num))
+            layers.append(nn.ReLU())
+            layers.append(nn.Dropout(p=0.2))
+            deep_input_dims = neuron_num
+        layers.append(nn.Linear(deep_input_dims, 1))
+        self.mlp = nn.Sequential(*layers)
+
+    def forward(self, x):
+        E, w, b = self.embedding.weight, self.linear.weight, self.bias
+        if torch.is_grad_enabled() and any(p.requires_grad for p in self.parameters()):
+            z_lin, flat = _WDPart.apply(x, E, w, b)
+            out = mlp_forward(self.mlp, flat, self.training)
+            return torch.sigmoid(z_lin + out)
+        with torch.no_grad():
+            z_lin, h = hip_ops.wd_forward(x, E.detach(), w.detach(), b.detach())
+            m = self.mlp
+            p0 = m[2].p if self.training else 0.0
+            p1 = m[5].p if self.training else 0.0
+            h = hip_ops.linear(h, m[0].weight, m[0].bias, relu=True, drop_p=p0,
+                               seed=_dropout_seed())
+            h = hip_ops.linear(h, m[3].weight, m[3].bias, relu=True, drop_p=p1,
+                               seed=_dropout_seed())
+            head = hip_ops.deepfm_head(h, m[6].weight, m[6].bias, z_lin)
+            return head["p"].view(-1, 1)
 
 
 class DeepFM(nn.Module):

@@ -1,18 +1,20 @@
 """CTR pretraining driver — counterpart of ``src/all_main/pretrain_main.py``.
 
 Same functions (setup_seed, get_model, get_dataset, train, test, submission, main,
-eva_stopping), same flags and files (train_.txt / test_.txt / featindex.txt in, rotating
+eva_stopping; plus build_model, which adds W&D and AFM to get_model's families), same
+flags and files (train_.txt / test_.txt / featindex.txt in, rotating
 ``{model}{epoch%5}.pth`` + ``{model}best.pth`` + ``test_submission.csv`` / ``day_aucs.csv``
 out), same semantics: batches in file order (no shuffle), Adam re-created every epoch
 (here: :meth:`FusedCTRTrainer.reset_optimizer`), train loss = mean of batch losses,
 AUC over the concatenated test predictions, loss-/AUC-based early stopping with reload
 of the checkpoint four epochs back.
 
-Differences, all deliberate: the training step is the fused HIP step (FM, DeepFM, IPNN
+Differences, all deliberate: the training step is the fused HIP step (FM, DeepFM, W&D, IPNN
 and OPNN; FFM: FusedFFMTrainer, the same deferred-exact Adam over its F*V field-table rows;
-LR, FNN and DCN: AutogradTrainer, the reference's own step — autograd over the HIP kernels and
-torch.optim.Adam — which also serves the other models for comparison; W&D and AFM
-are out of scope); the batches are
+LR, FNN, DCN and AFM: AutogradTrainer, the reference's own step — autograd over the HIP
+kernels and torch.optim.Adam — which also serves the other models for comparison; all ten
+families of the reference's p_model.py are built: main() builds its model through
+build_model, get_model itself keeps refusing W&D and AFM); the batches are
 sliced from one device-resident copy of the data instead of 8 DataLoader worker
 processes; the rotating-checkpoint cleanup skips files that were never written (the
 reference crashes there when epoch < 5, all_main/pretrain_main.py:201-202).
@@ -69,9 +71,20 @@ def get_model(model_name, feature_nums, field_nums, latent_dims):
         "built but OPNN too")
 
 
+def build_model(model_name, feature_nums, field_nums, latent_dims, fallback=None):
+    """The model of a family name, all ten of the reference's p_model.py: WideAndDeep for
+    "W&D", AFM for "AFM" (the reference driver's default), every other name through this
+    module's get_model, looked up when called (fallback: another module's get_model)."""
+    if model_name == "W&D":
+        return Model.WideAndDeep(feature_nums, field_nums, latent_dims)
+    if model_name == "AFM":
+        return Model.AFM(feature_nums, field_nums, latent_dims)
+    return (fallback or get_model)(model_name, feature_nums, field_nums, latent_dims)
+
+
 def make_trainer(model_name, model, learning_rate, weight_decay):
     """The training step of a model family: the fused HIP step where one exists (FM, DeepFM,
-    IPNN, OPNN; FFM), else the reference's own step through autograd (LR, FNN, DCN, AFM)."""
+    W&D, IPNN, OPNN; FFM), else the reference's own step through autograd (LR, FNN, DCN, AFM)."""
     if model_name == "FFM":
         return FusedFFMTrainer(model, lr=learning_rate, weight_decay=weight_decay)
     if model_name in ("LR", "FNN", "DCN", "AFM"):
@@ -273,7 +286,7 @@ def main(data_path, dataset_name, campaign_id, latent_dims, model_name, epoch, l
         train_dataset = Data.libsvm_dataset(train_data[:, 1:], train_data[:, 0])
         train_data_loader = DeviceBatches(train_dataset, batch_size, device)
 
-    model = get_model(model_name, feature_nums, field_nums, latent_dims).to(device)
+    model = build_model(model_name, feature_nums, field_nums, latent_dims).to(device)
     loss = nn.BCELoss()
     trainer = make_trainer(model_name, model, learning_rate, weight_decay)
 
@@ -306,7 +319,7 @@ def main(data_path, dataset_name, campaign_id, latent_dims, model_name, epoch, l
     end_time = datetime.datetime.now()
 
     if is_early_stop:
-        test_model = get_model(model_name, feature_nums, field_nums, latent_dims).to(device)
+        test_model = build_model(model_name, feature_nums, field_nums, latent_dims).to(device)
         load_path = save_param_dir + campaign_id + model_name + str(early_stop_index) + ".pth"
         test_model.load_state_dict(torch.load(load_path, map_location=device, weights_only=True))
     else:
@@ -337,7 +350,7 @@ def _parser():
     parser.add_argument("--data_path", default="../../data/")
     parser.add_argument("--dataset_name", default="avazu/", help="ipinyou, cretio, yoyi, avazu")
     parser.add_argument("--campaign_id", default="avazu/", help="1458, 3358, 3386, 3427, 3476, avazu")
-    parser.add_argument("--model_name", default="FM", help="LR, FM, FFM, DeepFM, IPNN, OPNN, FNN, DCN")
+    parser.add_argument("--model_name", default="FM", help="LR, FM, FFM, W&D, DeepFM, IPNN, OPNN, FNN, DCN, AFM")
     parser.add_argument("--latent_dims", type=int, default=10)
     parser.add_argument("--epoch", type=int, default=20)
     parser.add_argument("--learning_rate", type=float, default=1e-3)

@@ -51,7 +51,7 @@ import torch.distributed as dist
 
 from . import hip_ops
 from .distributed import allreduce_sum_, alltoall_equal, alltoallv, exchange_counts, world
-from .p_model import OuterPNN
+from .p_model import OuterPNN, WideAndDeep
 from .trainer import FusedCTRTrainer, InputSlot, graph_capture, live_pool
 
 CAP_QUANTUM = 1024  # exchange capacities are multiples of this many rows
@@ -154,6 +154,9 @@ class ShardedCTRTrainer(FusedCTRTrainer):
         blocks gave one owner ~85 % of every batch's unique rows and an exchange capacity of
         41,984 rows per pair against ~7,600 rows per owner on average (82 % padding); cyclic
         ownership spreads every field over every rank."""
+        if isinstance(model, WideAndDeep):  # before anything is allocated or sharded
+            raise TypeError("ShardedCTRTrainer does not drive WideAndDeep: row-sharded W&D is "
+                            "not built (FusedCTRTrainer drives it on one device)")
         if isinstance(model, OuterPNN):  # before anything is allocated or sharded
             raise TypeError("ShardedCTRTrainer does not drive OuterPNN: row-sharded OPNN is not "
                             "built (FusedCTRTrainer drives it on one device)")

@@ -38,7 +38,7 @@ import torch.nn as nn
 from . import hip_ops
 from ._lib import lib
 from .distributed import allgather_sparse_rows, allreduce_sum_, world
-from .p_model import FM, DeepFM, InnerPNN, OuterPNN
+from .p_model import FM, DeepFM, InnerPNN, OuterPNN, WideAndDeep
 
 
 @contextlib.contextmanager
@@ -97,9 +97,15 @@ DEEPFM_DENSE = ("bias", "mlp.0.weight", "mlp.0.bias", "mlp.3.weight", "mlp.3.bia
                 "mlp.6.weight", "mlp.6.bias")
 FM_DENSE = ("bias",)
 IPNN_DENSE = DEEPFM_DENSE[1:]  # InnerPNN: the MLP only (no linear term, no bias)
-_MLP_KINDS = ("DeepFM", "IPNN", "OPNN")
+_MLP_KINDS = ("DeepFM", "IPNN", "OPNN", "W&D")
 # the product networks: no linear table, per-slot embedding gradients (b.dslot) summed per row
 _PNN_KINDS = ("IPNN", "OPNN")
+
+
+def embedding_name(model: nn.Module) -> str:
+    """The submodule that holds a model's embedding table: ``embedding`` in WideAndDeep (the
+    reference's name there), ``feature_embedding`` in every other family."""
+    return "embedding" if isinstance(model, WideAndDeep) else "feature_embedding"
 
 
 class InputSlot:
@@ -158,7 +164,7 @@ class _Bufs:
 
 
 class FusedCTRTrainer:
-    """Fused forward + BCE + backward + dense Adam for FM / DeepFM.
+    """Fused forward + BCE + backward + dense Adam for FM / DeepFM / WideAndDeep / the PNNs.
 
     Args mirror ``torch.optim.Adam(model.parameters(), lr, betas, eps, weight_decay)``.
     The model's dense parameters (FM bias, DeepFM MLP) are re-pointed into one flat
@@ -169,15 +175,18 @@ class FusedCTRTrainer:
     def __init__(self, model: nn.Module, lr: float = 1e-3, weight_decay: float = 0.0,
                  betas=(0.9, 0.999), eps: float = 1e-8, process_group=None, seed: int | None = None,
                  optimizer_mode: str = "deferred"):
-        if not isinstance(model, (FM, DeepFM, InnerPNN, OuterPNN)):
-            raise TypeError("FusedCTRTrainer drives FM, DeepFM, InnerPNN or OuterPNN")
+        if not isinstance(model, (FM, DeepFM, InnerPNN, OuterPNN, WideAndDeep)):
+            raise TypeError("FusedCTRTrainer drives FM, DeepFM, WideAndDeep, InnerPNN or "
+                            "OuterPNN")
         self.model = model
         self.kind = ("DeepFM" if isinstance(model, DeepFM) else
+                     "W&D" if isinstance(model, WideAndDeep) else
                      "IPNN" if isinstance(model, InnerPNN) else
                      "OPNN" if isinstance(model, OuterPNN) else "FM")
         self.lr, self.weight_decay, self.betas, self.eps = float(lr), float(weight_decay), betas, eps
         self.group = process_group
-        E = model.feature_embedding.weight
+        self.emb_name = embedding_name(model) + ".weight"  # its state_dict key
+        E = self._table()
         self.device = E.device
         if self.device.type != "cuda":
             raise RuntimeError("FusedCTRTrainer needs the model on a ROCm device")
@@ -185,7 +194,7 @@ class FusedCTRTrainer:
         self._ksum_ptr = model.ksum().data_ptr() if self.kind == "OPNN" else None
         named = dict(model.named_parameters())
         self.dense_names = {"DeepFM": DEEPFM_DENSE, "FM": FM_DENSE, "IPNN": IPNN_DENSE,
-                            "OPNN": IPNN_DENSE}[self.kind]
+                            "OPNN": IPNN_DENSE, "W&D": DEEPFM_DENSE}[self.kind]
         # 16-B aligned views (offsets multiples of 4 floats): the GEMMs read the weights
         # through the float4 / LDS-DMA path only when a row start is 16-B aligned
         self.offsets, total = {}, 0
@@ -377,6 +386,10 @@ class FusedCTRTrainer:
         except Exception:  # interpreter shutdown
             pass
 
+    def _table(self) -> nn.Parameter:
+        """The model's embedding table Parameter (the one place that knows its name)."""
+        return getattr(self.model, embedding_name(self.model)).weight
+
     def _table_rows(self) -> tuple[int, int]:
         return 0, self.V
 
@@ -478,7 +491,7 @@ class FusedCTRTrainer:
         named = list(self.model.named_parameters())
         m = {n: v for n, v in zip(self.dense_names, self._split(self.m_flat))}
         v = {n: v for n, v in zip(self.dense_names, self._split(self.v_flat))}
-        m["feature_embedding.weight"], v["feature_embedding.weight"] = self.m_E, self.v_E
+        m[self.emb_name], v[self.emb_name] = self.m_E, self.v_E
         if self.m_w is not None:
             m["linear.weight"], v["linear.weight"] = self.m_w.view(-1, 1), self.v_w.view(-1, 1)
         state = {i: {"step": torch.tensor(float(self.step_count)), "exp_avg": m[n].clone(),
@@ -509,8 +522,11 @@ class FusedCTRTrainer:
         # MLP input width: IPNN appends the F(F-1)/2 pair products, OPNN the K cross columns
         W = F * K + {"IPNN": F * (F - 1) // 2, "OPNN": K}.get(self.kind, 0)
         # DeepFM writes its MLP input straight as planes (b.xp): no fp32 copy of X
-        x_fp32 = deep and not (self.kind in _PNN_KINDS or hip_ops.fm_forward_planes_ok(K, F))
-        fm = hip_ops.FMForward(z=e(B), sum_e=e(B, K), emb_out=e(B, W) if x_fp32 else None,
+        # (W&D's input kernel writes the planes for every K; it has no field sum either)
+        x_fp32 = deep and not (self.kind in _PNN_KINDS or self.kind == "W&D"
+                               or hip_ops.fm_forward_planes_ok(K, F))
+        fm = hip_ops.FMForward(z=e(B), sum_e=None if self.kind == "W&D" else e(B, K),
+                               emb_out=e(B, W) if x_fp32 else None,
                                p=None, loss_elem=e(B), gz=e(B))
         S = B * F
         b = _Bufs(B=B, fm=fm, plan=hip_ops.SparsePlanBuffers(S, dev), grad_rows=e(S, K),
@@ -914,7 +930,7 @@ class FusedCTRTrainer:
             y = y.float()
         y = y.contiguous()
         m = self.model
-        E, bias = m.feature_embedding.weight.data, self.views.get("bias")
+        E, bias = self._table().data, self.views.get("bias")
         w = m.linear.weight.data if self.kind not in _PNN_KINDS else None
         gv = self.grad_views
         step_hint = self.step_count + 1
@@ -1012,6 +1028,14 @@ class FusedCTRTrainer:
                                               out=b.grad_rows, keep_sums=self.keep_grads)
             else:
                 hip_ops.segment_sum_rows(b.plan, b.dslot, rowmap=sparse_rowmap, out=b.grad_rows)
+        elif self.kind == "W&D":  # a slot's gradient is its slice of dX, its linear one gz[b]
+            if fused:
+                hip_ops.wd_embedding_grad_adam(b.plan, F, gz, b.dx, table, **apply_kw,
+                                               grad_rows=b.grad_rows, grad_lin=b.grad_lin,
+                                               keep_sums=self.keep_grads)
+            else:
+                hip_ops.wd_embedding_grad(b.plan, F, self.K, gz, b.dx, sparse_rowmap,
+                                          grad_rows=b.grad_rows, grad_lin=b.grad_lin)
         elif fused:
             hip_ops.fm_embedding_grad_adam(b.plan, F, gz, b.fm.sum_e, b.dx, table, **apply_kw,
                                            grad_rows=b.grad_rows, grad_lin=b.grad_lin,
@@ -1122,6 +1146,10 @@ class FusedCTRTrainer:
             X = hip_ops.opnn_forward(x, E, self.model._ksum, out=None, err_flag=self.err,
                                      planes=b.xp, sum_e=b.fm.sum_e)
             z_fm = b.zero
+        elif self.kind == "W&D":  # flat(E[x]) as planes and the wide logit, one launch, any K
+            hip_ops.wd_forward(x, E, w, bias, out=None, err_flag=self.err, planes=b.xp,
+                               z_lin=b.fm.z)
+            X, z_fm = None, b.fm.z
         elif b.fm.emb_out is None:  # gather + FM, the MLP input written as its planes
             hip_ops.fm_forward_planes(x, E, w, bias, b.xp, b.fm.z, b.fm.sum_e, err_flag=self.err)
             X, z_fm = None, b.fm.z
