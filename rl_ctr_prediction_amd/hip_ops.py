@@ -1240,6 +1240,18 @@ def feature_embedding(idx: torch.Tensor, emb: torch.Tensor, err_flag=None,
     return out
 
 
+def _check_out_planes(who: str, out, planes, B: int, W: int) -> None:
+    """The MLP-input writers' checks of the fp32 `out` and the `planes` they may write (the
+    same with or without planes: the C side knows ldc only)."""
+    if out is not None:
+        _dev(out, "out")
+        if (out.dtype != torch.float32 or out.dim() != 2 or out.shape[0] < B
+                or out.shape[1] < W or out.stride(1) != 1):
+            raise ValueError(f"{who}: out must be float32 [>= {B}, >= {W}], unit column stride")
+    if planes is not None and (planes.rows < B or planes.cols < W):
+        raise ValueError(f"{who}: planes [{planes.rows}, {planes.cols}] < [{B}, {W}]")
+
+
 def ipnn_forward(idx: torch.Tensor, emb: torch.Tensor, out: torch.Tensor | None = None,
                  err_flag=None, planes: "Planes | None" = None) -> torch.Tensor | None:
     """InnerPNN MLP input [B, F*K + F(F-1)/2]: flat embeddings, then the pairwise inner
@@ -1251,15 +1263,8 @@ def ipnn_forward(idx: torch.Tensor, emb: torch.Tensor, out: torch.Tensor | None 
     B, F = idx.shape
     V, K = emb.shape
     W = F * K + F * (F - 1) // 2
-    if out is not None:  # the same checks with or without planes: the C side knows ldc only
-        _dev(out, "out")
-        if (out.dtype != torch.float32 or out.dim() != 2 or out.shape[0] < B
-                or out.shape[1] < W or out.stride(1) != 1):
-            raise ValueError(f"ipnn_forward: out must be float32 [>= {B}, >= {W}], unit "
-                             "column stride")
+    _check_out_planes("ipnn_forward", out, planes, B, W)
     if planes is not None:
-        if planes.rows < B or planes.cols < W:
-            raise ValueError(f"ipnn_forward: planes [{planes.rows}, {planes.cols}] < [{B}, {W}]")
         lib.ctr_ipnn_forward_planes(_p(idx), it, B, F, K, V, _p(emb), _p(out),
                                     out.stride(0) if out is not None else 0, planes.desc,
                                     _p(err_flag), _stream())
@@ -1304,14 +1309,7 @@ def opnn_forward(idx: torch.Tensor, emb: torch.Tensor, ksum: torch.Tensor,
     W = F * K + K
     if ksum.numel() != K:
         raise ValueError(f"opnn_forward: ksum must hold K = {K} values, got {ksum.numel()}")
-    if out is not None:
-        _dev(out, "out")
-        if (out.dtype != torch.float32 or out.dim() != 2 or out.shape[0] < B
-                or out.shape[1] < W or out.stride(1) != 1):
-            raise ValueError(f"opnn_forward: out must be float32 [>= {B}, >= {W}], unit "
-                             "column stride")
-    if planes is not None and (planes.rows < B or planes.cols < W):
-        raise ValueError(f"opnn_forward: planes [{planes.rows}, {planes.cols}] < [{B}, {W}]")
+    _check_out_planes("opnn_forward", out, planes, B, W)
     if sum_e is not None:
         _f32(sum_e, "sum_e")
         if sum_e.numel() < B * K:
@@ -1371,14 +1369,7 @@ def wd_forward(idx: torch.Tensor, emb: torch.Tensor, lin: torch.Tensor, bias: to
     W = F * K
     if lin.numel() != V or bias.numel() != 1:
         raise ValueError(f"wd_forward: linear.weight must hold V = {V} values and bias one")
-    if out is not None:
-        _dev(out, "out")
-        if (out.dtype != torch.float32 or out.dim() != 2 or out.shape[0] < B
-                or out.shape[1] < W or out.stride(1) != 1):
-            raise ValueError(f"wd_forward: out must be float32 [>= {B}, >= {W}], unit column "
-                             "stride")
-    if planes is not None and (planes.rows < B or planes.cols < W):
-        raise ValueError(f"wd_forward: planes [{planes.rows}, {planes.cols}] < [{B}, {W}]")
+    _check_out_planes("wd_forward", out, planes, B, W)
     if z_lin is None:
         z_lin = torch.empty(B, dtype=torch.float32, device=emb.device)
     elif _f32(z_lin, "z_lin").numel() < B:

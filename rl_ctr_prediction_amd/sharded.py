@@ -839,35 +839,31 @@ class ShardedCTRTrainer(FusedCTRTrainer):
     def _sharded_fwd_bwd(self, ids, y, b, T, T_lin, bias, mean_div, F):
         """Forward + backward over the compact table T (ids: slot -> unique ordinal), the
         per-row gradient sums into b.grad_rows / b.grad_lin (plan order); returns gz."""
-        gv = self.grad_views
-        B = ids.shape[0]
-        if self.kind == "FM":
+        gv, B, spec = self.grad_views, ids.shape[0], self.spec
+        slots = spec.slot_grads is not None  # per-slot gradients in b.dslot, summed per row
+        if spec.mlp:
+            gz = self._mlp_forward_backward(ids, y, b, T, T_lin, bias, mean_div)
+        else:
             t = self._mark("gather")
             hip_ops.fm_forward(ids, T, T_lin, bias, want_sum=True, labels=y, mean_div=mean_div,
                                want_p=False, out=b.fm)
             self._span("gather", t)
             gz = b.fm.gz
             hip_ops.tensor_sum(gz, out=gv["bias"].view(1))
-        else:
-            gz = self._deepfm_forward_backward(ids, y, b, T, T_lin, bias, mean_div)
         t = self._mark("scatter")
         xb = getattr(self, "_xb_cur", None)
         if xb is not None and self._grads_to_chunks and not self.keep_grads:
             # the row sums straight into the exchange chunks (no compact sums + pack pass)
-            if self.kind == "IPNN":
-                hip_ops.shard_row_grads(b.plan, xb.C, xb.offsets, xb.g_out, K=self.K,
-                                        vals=b.dslot)
-            else:
-                hip_ops.shard_row_grads(b.plan, xb.C, xb.offsets, xb.g_out, K=self.K, F=F, emb=T,
-                                        gz=gz, sum_e=b.fm.sum_e, dx=b.dx,
-                                        lin=T_lin is not None)
-        elif self.kind == "IPNN":  # per-slot gradients (through the pair products) summed per row
+            kw = dict(vals=b.dslot) if slots else dict(F=F, emb=T, gz=gz, sum_e=b.fm.sum_e,
+                                                       dx=b.dx, lin=T_lin is not None)
+            hip_ops.shard_row_grads(b.plan, xb.C, xb.offsets, xb.g_out, K=self.K, **kw)
+        elif slots:
             hip_ops.segment_sum_rows(b.plan, b.dslot, out=b.grad_rows)
         else:
             hip_ops.fm_embedding_grad(b.plan, F, T, gz, b.fm.sum_e, b.dx, None,
                                       grad_rows=b.grad_rows, grad_lin=b.grad_lin, compact=True)
         self._span("scatter", t)
-        if self.kind != "FM":  # the dense-parameter gradients, on the weight-gradient stream
+        if spec.mlp:  # the dense-parameter gradients, on the weight-gradient stream
             self._weight_grads(b, gz)
         else:
             hip_ops.tensor_sum(b.fm.loss_elem, scale=1.0 / B, out=b.loss)

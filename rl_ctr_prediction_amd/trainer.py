@@ -36,7 +36,6 @@ import torch
 import torch.nn as nn
 
 from . import hip_ops
-from ._lib import lib
 from .distributed import allgather_sparse_rows, allreduce_sum_, world
 from .p_model import FM, DeepFM, InnerPNN, OuterPNN, WideAndDeep
 
@@ -86,26 +85,113 @@ def flush_hooks(model: nn.Module, trainer) -> None:
     model._register_load_state_dict_pre_hook(drain)
 
 
-class _nullctx:
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *exc):
-        return False
-
 DEEPFM_DENSE = ("bias", "mlp.0.weight", "mlp.0.bias", "mlp.3.weight", "mlp.3.bias",
                 "mlp.6.weight", "mlp.6.bias")
-FM_DENSE = ("bias",)
-IPNN_DENSE = DEEPFM_DENSE[1:]  # InnerPNN: the MLP only (no linear term, no bias)
-_MLP_KINDS = ("DeepFM", "IPNN", "OPNN", "W&D")
-# the product networks: no linear table, per-slot embedding gradients (b.dslot) summed per row
-_PNN_KINDS = ("IPNN", "OPNN")
 
 
 def embedding_name(model: nn.Module) -> str:
     """The submodule that holds a model's embedding table: ``embedding`` in WideAndDeep (the
     reference's name there), ``feature_embedding`` in every other family."""
     return "embedding" if isinstance(model, WideAndDeep) else "feature_embedding"
+
+
+@dataclass(frozen=True)
+class _Kind:
+    """What the fused step needs to know about one model class; the _KINDS table below is the
+    only place that tells the kinds apart. The three functions are the kind's own launches,
+    called from _launch alone (eager and capture steps, never a replay): mlp_input fills the
+    MLP input planes b.xp and returns the logit the head adds to the MLP's, slot_grads turns
+    b.dx into the per-slot gradients b.dslot, scatter sums the gradients per plan row into
+    b.grad_rows / b.grad_lin or (fused) applies the sums where they complete."""
+    name: str                   # FusedCTRTrainer.kind
+    model: type
+    dense: tuple                # dense parameter names, in flat-buffer order
+    scatter: object             # (tr, b, F, gz, fused, table, apply_kw, rowmap)
+    mlp_input: object = None    # (tr, x, b, E, w, bias) -> z_fm; None: no MLP part
+    slot_grads: object = None   # (tr, x, b, E); None: the scatter forms a slot's gradient
+    linear: bool = True         # has linear.weight (else every lin pointer of the ABI is NULL)
+    field_sum: bool = True      # the forward saves sum_f e_f in b.fm.sum_e
+    ksum: bool = False          # the launches read the model's kernel.sum(0) cache (ksum())
+    extra_cols: object = lambda F, K: 0    # MLP-input columns beyond F*K
+    x_fp32: object = lambda K, F: False    # X is written as fp32 (b.fm.emb_out), then split
+    mlp = property(lambda self: self.mlp_input is not None)
+
+
+def _deepfm_input(tr, x, b, E, w, bias):
+    if b.fm.emb_out is None:  # gather + FM, the MLP input written as its planes
+        hip_ops.fm_forward_planes(x, E, w, bias, b.xp, b.fm.z, b.fm.sum_e, err_flag=tr.err)
+    else:
+        hip_ops.fm_forward(x, E, w, bias, want_sum=True, want_emb=True, want_p=False,
+                           err_flag=tr.err, out=b.fm)
+        hip_ops.split_planes(b.fm.emb_out, out=b.xp)
+    return b.fm.z
+
+
+def _fm_scatter(tr, b, F, gz, fused, table, apply_kw, rowmap):  # DeepFM and (b.dx None) FM
+    if not fused:
+        return hip_ops.fm_embedding_grad(b.plan, F, table[0], gz, b.fm.sum_e, b.dx, rowmap,
+                                         grad_rows=b.grad_rows, grad_lin=b.grad_lin)
+    hip_ops.fm_embedding_grad_adam(b.plan, F, gz, b.fm.sum_e, b.dx, table, **apply_kw,
+                                   grad_rows=b.grad_rows, grad_lin=b.grad_lin,
+                                   keep_sums=tr.keep_grads)
+
+
+def _wd_input(tr, x, b, E, w, bias):  # flat(E[x]) as planes and the wide logit, any K
+    hip_ops.wd_forward(x, E, w, bias, out=None, err_flag=tr.err, planes=b.xp, z_lin=b.fm.z)
+    return b.fm.z
+
+
+def _wd_scatter(tr, b, F, gz, fused, table, apply_kw, rowmap):  # dX's slices and gz[b]
+    if not fused:
+        return hip_ops.wd_embedding_grad(b.plan, F, tr.K, gz, b.dx, rowmap,
+                                         grad_rows=b.grad_rows, grad_lin=b.grad_lin)
+    hip_ops.wd_embedding_grad_adam(b.plan, F, gz, b.dx, table, **apply_kw,
+                                   grad_rows=b.grad_rows, grad_lin=b.grad_lin,
+                                   keep_sums=tr.keep_grads)
+
+
+def _ipnn_input(tr, x, b, E, w, bias):  # flat(E[x]) ++ pairwise inner products, as planes
+    hip_ops.ipnn_forward(x, E, out=None, err_flag=tr.err, planes=b.xp)
+    return b.zero  # no FM logit
+
+
+def _ipnn_slot_grads(tr, x, b, E):  # through the pair products
+    hip_ops.ipnn_backward(x, E, b.dx, out=b.dslot)
+
+
+def _opnn_input(tr, x, b, E, w, bias):  # flat(E[x]) ++ ksum * (sum_f e_f)^2, as planes, and
+    # the field sums in b.fm.sum_e for the backward (one launch writes both)
+    hip_ops.opnn_forward(x, E, tr.model._ksum, out=None, err_flag=tr.err, planes=b.xp,
+                         sum_e=b.fm.sum_e)
+    return b.zero  # no FM logit
+
+
+def _opnn_slot_grads(tr, x, b, E):  # from dX and the saved field sums
+    hip_ops.opnn_backward(b.fm.sum_e, tr.model._ksum, b.dx, x.shape[1], out=b.dslot)
+
+
+def _slot_scatter(tr, b, F, gz, fused, table, apply_kw, rowmap):  # b.dslot summed per row
+    if not fused:
+        return hip_ops.segment_sum_rows(b.plan, b.dslot, rowmap=rowmap, out=b.grad_rows)
+    hip_ops.segment_sum_rows_adam(b.plan, b.dslot, None, table, **apply_kw,
+                                  out=b.grad_rows, keep_sums=tr.keep_grads)
+
+
+_KINDS = (  # resolved by isinstance, first match
+    _Kind("DeepFM", DeepFM, DEEPFM_DENSE, _fm_scatter, _deepfm_input,
+          x_fp32=lambda K, F: not hip_ops.fm_forward_planes_ok(K, F)),
+    _Kind("W&D", WideAndDeep, DEEPFM_DENSE, _wd_scatter, _wd_input, field_sum=False),
+    _Kind("IPNN", InnerPNN, DEEPFM_DENSE[1:], _slot_scatter, _ipnn_input, _ipnn_slot_grads,
+          linear=False, extra_cols=lambda F, K: F * (F - 1) // 2),
+    _Kind("OPNN", OuterPNN, DEEPFM_DENSE[1:], _slot_scatter, _opnn_input, _opnn_slot_grads,
+          linear=False, ksum=True, extra_cols=lambda F, K: K),
+    _Kind("FM", FM, ("bias",), _fm_scatter),
+)
+_MLP_KINDS = tuple(sorted(k.name for k in _KINDS if k.mlp))
+
+
+def _kind_of(model: nn.Module) -> _Kind | None:  # None: the fused step does not drive it
+    return next((k for k in _KINDS if isinstance(model, k.model)), None)
 
 
 class InputSlot:
@@ -164,7 +250,8 @@ class _Bufs:
 
 
 class FusedCTRTrainer:
-    """Fused forward + BCE + backward + dense Adam for FM / DeepFM / WideAndDeep / the PNNs.
+    """Fused forward + BCE + backward + dense Adam for FM / DeepFM / WideAndDeep / the PNNs:
+    the model classes of the _KINDS table, whose entries hold all that differs between them.
 
     Args mirror ``torch.optim.Adam(model.parameters(), lr, betas, eps, weight_decay)``.
     The model's dense parameters (FM bias, DeepFM MLP) are re-pointed into one flat
@@ -175,14 +262,12 @@ class FusedCTRTrainer:
     def __init__(self, model: nn.Module, lr: float = 1e-3, weight_decay: float = 0.0,
                  betas=(0.9, 0.999), eps: float = 1e-8, process_group=None, seed: int | None = None,
                  optimizer_mode: str = "deferred"):
-        if not isinstance(model, (FM, DeepFM, InnerPNN, OuterPNN, WideAndDeep)):
+        spec = self.spec = _kind_of(model)
+        if spec is None:
             raise TypeError("FusedCTRTrainer drives FM, DeepFM, WideAndDeep, InnerPNN or "
                             "OuterPNN")
         self.model = model
-        self.kind = ("DeepFM" if isinstance(model, DeepFM) else
-                     "W&D" if isinstance(model, WideAndDeep) else
-                     "IPNN" if isinstance(model, InnerPNN) else
-                     "OPNN" if isinstance(model, OuterPNN) else "FM")
+        self.kind = spec.name
         self.lr, self.weight_decay, self.betas, self.eps = float(lr), float(weight_decay), betas, eps
         self.group = process_group
         self.emb_name = embedding_name(model) + ".weight"  # its state_dict key
@@ -191,10 +276,9 @@ class FusedCTRTrainer:
         if self.device.type != "cuda":
             raise RuntimeError("FusedCTRTrainer needs the model on a ROCm device")
         self.V, self.K = self._vocab_size(E), E.shape[1]
-        self._ksum_ptr = model.ksum().data_ptr() if self.kind == "OPNN" else None
+        self._ksum_ptr = model.ksum().data_ptr() if spec.ksum else None
         named = dict(model.named_parameters())
-        self.dense_names = {"DeepFM": DEEPFM_DENSE, "FM": FM_DENSE, "IPNN": IPNN_DENSE,
-                            "OPNN": IPNN_DENSE, "W&D": DEEPFM_DENSE}[self.kind]
+        self.dense_names = spec.dense
         # 16-B aligned views (offsets multiples of 4 floats): the GEMMs read the weights
         # through the float4 / LDS-DMA path only when a row start is 16-B aligned
         self.offsets, total = {}, 0
@@ -225,9 +309,8 @@ class FusedCTRTrainer:
         n_rows = self.E_tab.shape[0]  # V_tab (+ a spare row under row sharding)
         self.m_E = torch.zeros_like(self.E_tab)
         self.v_E = torch.zeros_like(self.E_tab)
-        if self.kind in _PNN_KINDS:  # no linear table: every lin pointer of the ABI is NULL
-            self.w_tab = self.m_w = self.v_w = None
-        else:
+        self.w_tab = self.m_w = self.v_w = None  # no linear table: the ABI's lin pointers NULL
+        if spec.linear:
             self.w_tab = self._own_rows(model.linear.weight.data)
             self.m_w = torch.zeros(n_rows, dtype=torch.float32, device=self.device)
             self.v_w = torch.zeros_like(self.m_w)
@@ -251,7 +334,7 @@ class FusedCTRTrainer:
         # path (FM: the forward / backward are short; C2 31.6 vs 28.4 M ex/s), the catch-up
         # and forward first where they are (MLP kinds; C3 12.39 vs 11.67 M ex/s)
         env = os.environ.get("CTR_PLAN_FIRST")
-        self.plan_first = (env == "1") if env in ("0", "1") else self.kind == "FM"
+        self.plan_first = (env == "1") if env in ("0", "1") else not spec.mlp
         self.keep_grads = False
         # input staging (single process): every batch is copied into a fixed slot of its
         # shape (InputSlot) and the step graph of that slot is replayed, so fresh batches
@@ -297,7 +380,7 @@ class FusedCTRTrainer:
         # map two independent side lists onto one hardware queue in the wrong order (seen
         # with three: the plan queued behind the weight gradients, +100 us per step)
         self._wgrad_stream = None
-        if self.kind in _MLP_KINDS:
+        if spec.mlp:
             self._wgrad_stream = self._side if self._side is not None else self._new_stream()
             # Measured and not kept: this stream on a fraction of the CUs (CTR_WGRAD_CU_FRAC,
             # hip_ops.cu_masked_stream). The mask holds for eager launches only
@@ -307,9 +390,8 @@ class FusedCTRTrainer:
         # the MLP weights' planes: rewritten by the dense Adam with every update
         # (ctr_adam_dense_planes), re-split from the fp32 parameters (the source of truth:
         # state_dict / load_state_dict see fp32) whenever those changed outside the trainer
-        self._wplanes = None
-        self._wver = None
-        if self.kind in _MLP_KINDS:
+        self._wplanes = self._wver = None
+        if spec.mlp:
             w0, w1 = self.views["mlp.0.weight"], self.views["mlp.3.weight"]
             self._wplanes = (hip_ops.Planes(*w0.shape, self.device),
                              hip_ops.Planes(*w1.shape, self.device))
@@ -350,7 +432,7 @@ class FusedCTRTrainer:
         # contention (105 -> 76 us) but the gather beside dW0 takes 85 us instead of 28
         # (profiles/r05_pipelined_tail.txt)
         env = os.environ.get("CTR_PIPELINE_WGRAD")
-        self._pipe = (self.kind in _MLP_KINDS and self.deferred and self._side is not None
+        self._pipe = (spec.mlp and self.deferred and self._side is not None
                       and world()[1] == 1 and env == "1")
         # (bufset, X planes, their index) of the step whose dW0 + MLP Adam is pending
         self._tail = None
@@ -414,30 +496,11 @@ class FusedCTRTrainer:
             ev.record()
             self.timing[key].append((start, ev, work))
 
-    def _gemm(self, *args, **kw):
-        """hip_ops.gemm with a timing span carrying the product's flop count."""
-        t = self._mark("gemm")
-        out = hip_ops.gemm(*args, **kw)
-        if t is not None:
-            a, bb = args[0], args[1]
-            ta, tb = kw.get("trans_a", False), kw.get("trans_b", False)
-            M, K = (a.shape[1], a.shape[0]) if ta else a.shape
-            N = bb.shape[0] if tb else bb.shape[1]
-            self._span("gemm", t, 2.0 * M * N * K)
-        return out
-
     def _gemm_planes(self, a, b, a_rc, b_rc, M, N, K, **kw):
         """hip_ops.gemm_planes with a timing span carrying the product's flop count."""
         t = self._mark("gemm")
         out = hip_ops.gemm_planes(a, b, a_rc, b_rc, **kw)
         self._span("gemm", t, 2.0 * M * N * K)
-        return out
-
-    def _linear(self, x, w, b, **kw):
-        t = self._mark("gemm")
-        out = hip_ops.linear(x, w, b, **kw)
-        if t is not None:
-            self._span("gemm", t, 2.0 * x.shape[0] * w.shape[0] * x.shape[1])
         return out
 
     # ----------------------------------------------------------------- optimiser -----
@@ -518,21 +581,16 @@ class FusedCTRTrainer:
             return b
         dev, K = self.device, self.K
         e = lambda *s: torch.empty(*s, dtype=torch.float32, device=dev)  # noqa: E731
-        deep = self.kind in _MLP_KINDS
-        # MLP input width: IPNN appends the F(F-1)/2 pair products, OPNN the K cross columns
-        W = F * K + {"IPNN": F * (F - 1) // 2, "OPNN": K}.get(self.kind, 0)
-        # DeepFM writes its MLP input straight as planes (b.xp): no fp32 copy of X
-        # (W&D's input kernel writes the planes for every K; it has no field sum either)
-        x_fp32 = deep and not (self.kind in _PNN_KINDS or self.kind == "W&D"
-                               or hip_ops.fm_forward_planes_ok(K, F))
-        fm = hip_ops.FMForward(z=e(B), sum_e=None if self.kind == "W&D" else e(B, K),
-                               emb_out=e(B, W) if x_fp32 else None,
+        spec = self.spec
+        W = F * K + spec.extra_cols(F, K)  # MLP input width (emb_out: its fp32 copy, if any)
+        fm = hip_ops.FMForward(z=e(B), sum_e=e(B, K) if spec.field_sum else None,
+                               emb_out=e(B, W) if spec.x_fp32(K, F) else None,
                                p=None, loss_elem=e(B), gz=e(B))
         S = B * F
         b = _Bufs(B=B, fm=fm, plan=hip_ops.SparsePlanBuffers(S, dev), grad_rows=e(S, K),
                   grad_lin=e(S), loss=e(1))
         b.plan_own = b.plan
-        if deep:
+        if spec.mlp:
             mlp = self.model.mlp
             H1, H2 = mlp[0].out_features, mlp[3].out_features
             b.h1, b.h2, b.dx = e(B, H1), e(B, H2), e(B, W)
@@ -545,9 +603,8 @@ class FusedCTRTrainer:
             b.xps = {0: b.xp} if self._pipe else None
             b.h1p = P(B, H1, dev, ones_col=True)
             b.dh2p, b.dh1p = P(B, H2, dev), P(B, H1, dev)
-            if self.kind in _PNN_KINDS:
-                b.dslot = e(S, K)
-                b.zero = torch.zeros(B, dtype=torch.float32, device=dev)
+            if spec.slot_grads is not None:  # the product networks
+                b.dslot, b.zero = e(S, K), torch.zeros(B, dtype=torch.float32, device=dev)
             # dH2 goes to the GEMMs as planes only: no fp32 copy (6.5 MB a step at C3)
             b.head = dict(z=e(B), p=e(B), loss_elem=fm.loss_elem, gz=fm.gz, dh_pre=None)
         rank, ws = world()
@@ -613,14 +670,12 @@ class FusedCTRTrainer:
         B, F = x.shape
         rank, ws = world()
         mean_div = float(global_batch if global_batch is not None else B * ws)
-        if self.kind == "OPNN":
-            # kernel.sum(0), refreshed in place before anything is enqueued or captured: a
-            # replayed graph reads the buffer's current values. The step's launches (and the
-            # captured graphs) hold the buffer's address, like the parameters' views
-            if self.model.ksum().data_ptr() != self._ksum_ptr:
-                raise RuntimeError("FusedCTRTrainer: the OuterPNN's ksum buffer was replaced "
-                                   "(model.to(...) after the trainer was built?); build a new "
-                                   "trainer for the moved model")
+        # OPNN's kernel.sum(0), refreshed in place before anything is enqueued or captured: a
+        # replayed graph reads its current values, every launch and graph holds its address
+        if self._ksum_ptr is not None and self.model.ksum().data_ptr() != self._ksum_ptr:
+            raise RuntimeError("FusedCTRTrainer: the OuterPNN's ksum buffer was replaced "
+                               "(model.to(...) after the trainer was built?); build a new "
+                               "trainer for the moved model")
         self._sync_weight_planes()
         self._bound_staleness()
         if ws != 1:  # replicated data parallel: eager (the exchange sizes live on the host)
@@ -806,19 +861,17 @@ class FusedCTRTrainer:
     def _xkey(x):
         return (x.data_ptr(), tuple(x.shape), x.dtype, tuple(x.stride()), x.device)
 
-    def _weights_version(self):
-        mlp = self.model.mlp
-        return (mlp[0].weight._version, mlp[3].weight._version)
-
     def _sync_weight_planes(self, force: bool = False) -> None:
         """Re-split the MLP weights' planes if the fp32 weights changed outside the trainer
         (load_state_dict, in-place ops on the Parameters: their version counters move).
         Writes through ``.data`` bypass the counters: call sync_weights() after those."""
         if self._wplanes is None:
             return
-        ver = self._weights_version()
-        if force or ver != self._wver:
-            self._split_weights()
+        mlp = self.model.mlp
+        ver = (mlp[0].weight._version, mlp[3].weight._version)
+        if force or ver != self._wver:  # re-split from the fp32 parameters
+            for name, pl in zip(("mlp.0.weight", "mlp.3.weight"), self._wplanes):
+                hip_ops.split_planes(self.views[name], out=pl)
             self._wver = ver
 
     def sync_weights(self) -> None:
@@ -929,12 +982,11 @@ class FusedCTRTrainer:
         if y.dtype != torch.float32:
             y = y.float()
         y = y.contiguous()
-        m = self.model
+        spec = self.spec
         E, bias = self._table().data, self.views.get("bias")
-        w = m.linear.weight.data if self.kind not in _PNN_KINDS else None
+        w = self.model.linear.weight.data if spec.linear else None
         gv = self.grad_views
         step_hint = self.step_count + 1
-        self._ev_wplanes = None
         if self._side is not None:
             # the sparse plan is only needed from the scatter on: build it on a side stream
             # while the catch-up (plan-free, from the ids) and the forward run here.
@@ -997,18 +1049,18 @@ class FusedCTRTrainer:
                                            b.plan, step_hint, self.step_table, self.betas,
                                            self.eps, self.weight_decay, step_dev=self.step_done)
                 self._span("catchup", t)
-        if self.kind == "FM":
+        if spec.mlp:
+            gz = self._mlp_forward_backward(x, y, b, E, w, bias, mean_div)
+        else:  # FM: the forward with the BCE head
             t = self._mark("gather")
             hip_ops.fm_forward(x, E, w, bias, want_sum=True, labels=y, mean_div=mean_div,
                                want_p=False, err_flag=self.err, out=b.fm)
             self._span("gather", t)
             gz = b.fm.gz
-        else:
-            gz = self._deepfm_forward_backward(x, y, b, E, w, bias, mean_div)
         # FM, one process: the bias gradient, the batch loss, the dense Adam and the step
         # counter in one launch at the end of the step (ctr_fm_step_tail)
-        tail = self.kind == "FM" and ws == 1 and self._wplanes is None
-        if self.kind == "FM" and not tail:  # MLP kinds: on the weight-gradient stream
+        tail = not spec.mlp and ws == 1
+        if not spec.mlp and not tail:  # MLP kinds: on the weight-gradient stream
             hip_ops.tensor_sum(gz, out=gv["bias"].view(1))
         if self._side is not None and not have_plan:
             hip_ops.current_stream().wait_event(ev_plan)  # the plan
@@ -1022,31 +1074,11 @@ class FusedCTRTrainer:
         table = (E, self.m_E, self.v_E, w, self.m_w, self.v_w, self.last)
         apply_kw = dict(step_dev=self.step_cur, step_table=self.step_table, step=step_hint,
                         betas=self.betas, eps=self.eps, weight_decay=self.weight_decay)
-        if self.kind in _PNN_KINDS:
-            if fused:
-                hip_ops.segment_sum_rows_adam(b.plan, b.dslot, None, table, **apply_kw,
-                                              out=b.grad_rows, keep_sums=self.keep_grads)
-            else:
-                hip_ops.segment_sum_rows(b.plan, b.dslot, rowmap=sparse_rowmap, out=b.grad_rows)
-        elif self.kind == "W&D":  # a slot's gradient is its slice of dX, its linear one gz[b]
-            if fused:
-                hip_ops.wd_embedding_grad_adam(b.plan, F, gz, b.dx, table, **apply_kw,
-                                               grad_rows=b.grad_rows, grad_lin=b.grad_lin,
-                                               keep_sums=self.keep_grads)
-            else:
-                hip_ops.wd_embedding_grad(b.plan, F, self.K, gz, b.dx, sparse_rowmap,
-                                          grad_rows=b.grad_rows, grad_lin=b.grad_lin)
-        elif fused:
-            hip_ops.fm_embedding_grad_adam(b.plan, F, gz, b.fm.sum_e, b.dx, table, **apply_kw,
-                                           grad_rows=b.grad_rows, grad_lin=b.grad_lin,
-                                           keep_sums=self.keep_grads)
-        else:
-            hip_ops.fm_embedding_grad(b.plan, F, E, gz, b.fm.sum_e, b.dx, sparse_rowmap,
-                                      grad_rows=b.grad_rows, grad_lin=b.grad_lin)
+        spec.scatter(self, b, F, gz, fused, table, apply_kw, sparse_rowmap)
         self._span("scatter", t)
-        if self.kind in _MLP_KINDS:  # captured after the scatter: see the capture-order note
+        if spec.mlp:  # captured after the scatter: see the capture-order note
             self._weight_grads(b, gz)
-        if self.kind == "FM" and not tail:  # MLP kinds: on the weight-gradient stream
+        elif not tail:  # MLP kinds: on the weight-gradient stream
             hip_ops.tensor_sum(b.fm.loss_elem, scale=1.0 / B, out=b.loss)
         grad_rows, grad_lin, plan = b.grad_rows, (b.grad_lin if w is not None else None), b.plan
         if ws > 1:
@@ -1080,7 +1112,7 @@ class FusedCTRTrainer:
         wg = self._wgrad_stream if ws == 1 else None
         if wg is None:
             self._join_wgrad()
-        with torch.cuda.stream(wg) if wg is not None else _nullctx():
+        with torch.cuda.stream(wg) if wg is not None else contextlib.nullcontext():
             # pipelined: the FM bias now (the next step's gather reads it), the MLP at the
             # start of the next step (_tail_launch)
             self._adam_dense(step_hint, part="bias" if piped else "all")
@@ -1117,11 +1149,11 @@ class FusedCTRTrainer:
         for name, pl in resplit:
             hip_ops.split_planes(self.views[name], out=pl)
 
-    def _deepfm_forward_backward(self, x, y, b: _Bufs, E, w, bias, mean_div):
-        """The MLP part of DeepFM / InnerPNN (p_model.py:276-293,322 and 185-200) on
-        pre-split planes: 6 GEMMs per step, every operand read in the orientation its
-        producer wrote it (the transposed products of the backward by the GEMM's transpose
-        read), no transposed copy anywhere."""
+    def _mlp_forward_backward(self, x, y, b: _Bufs, E, w, bias, mean_div):
+        """The MLP part of every MLP kind (DeepFM's: p_model.py:276-293,322), between the
+        kind's input and slot-gradient launches (_Kind), on pre-split planes: 6 GEMMs per step,
+        every operand read in the orientation its producer wrote it (the transposed products
+        of the backward by the GEMM's transpose read), no transposed copy anywhere."""
         mlp, gv, vw = self.model.mlp, self.grad_views, self.views
         training = self.model.training
         p0 = float(mlp[2].p) if training else 0.0
@@ -1138,27 +1170,7 @@ class FusedCTRTrainer:
         off1 = rank * B * H1
         off2 = ws * B * H1 + rank * B * H2
         t = self._mark("gather")
-        if self.kind == "IPNN":  # cat = flat(E[x]) ++ pairwise inner products, as planes
-            X = hip_ops.ipnn_forward(x, E, out=None, err_flag=self.err, planes=b.xp)
-            z_fm = b.zero
-        elif self.kind == "OPNN":  # cat = flat(E[x]) ++ ksum * (sum_f e_f)^2, as planes; the
-            # field sums stay in b.fm.sum_e for the backward (one launch writes both)
-            X = hip_ops.opnn_forward(x, E, self.model._ksum, out=None, err_flag=self.err,
-                                     planes=b.xp, sum_e=b.fm.sum_e)
-            z_fm = b.zero
-        elif self.kind == "W&D":  # flat(E[x]) as planes and the wide logit, one launch, any K
-            hip_ops.wd_forward(x, E, w, bias, out=None, err_flag=self.err, planes=b.xp,
-                               z_lin=b.fm.z)
-            X, z_fm = None, b.fm.z
-        elif b.fm.emb_out is None:  # gather + FM, the MLP input written as its planes
-            hip_ops.fm_forward_planes(x, E, w, bias, b.xp, b.fm.z, b.fm.sum_e, err_flag=self.err)
-            X, z_fm = None, b.fm.z
-        else:
-            fm = hip_ops.fm_forward(x, E, w, bias, want_sum=True, want_emb=True, want_p=False,
-                                    err_flag=self.err, out=b.fm)
-            X, z_fm = fm.emb_out, fm.z
-        if X is not None:
-            hip_ops.split_planes(X, out=b.xp)
+        z_fm = self.spec.mlp_input(self, x, b, E, w, bias)
         self._span("gather", t)
         if getattr(b, "ev_tail", None) is not None:  # the previous step's MLP Adam
             hip_ops.current_stream().wait_event(b.ev_tail)
@@ -1183,19 +1195,11 @@ class FusedCTRTrainer:
                           epi=hip_ops.EPI_GRAD_MASK, aux=b.h1, scale=1.0 / (1.0 - p0))
         # Linear(F*K,300): dX = dH1 @ W0, the MLP-input gradient the scatter needs
         self._gemm_planes(b.dh1p, w0p, False, True, B, W, H1, out=b.dx)
-        if self.kind == "IPNN":  # per-slot embedding gradients through the pair products
-            hip_ops.ipnn_backward(x, E, b.dx, out=b.dslot)
-        elif self.kind == "OPNN":  # per-slot gradients from dX and the saved field sums
-            hip_ops.opnn_backward(b.fm.sum_e, self.model._ksum, b.dx, x.shape[1], out=b.dslot)
+        if self.spec.slot_grads is not None:
+            self.spec.slot_grads(self, x, b, E)
         b.ev_dx = torch.cuda.Event()
         b.ev_dx.record()
         return gz
-
-    def _split_weights(self) -> None:
-        """The MLP weights' bf16 planes, re-split from the fp32 parameters every step."""
-        w0p, w1p = self._wplanes
-        hip_ops.split_planes(self.views["mlp.0.weight"], out=w0p)
-        hip_ops.split_planes(self.views["mlp.3.weight"], out=w1p)
 
     def _weight_grads(self, b: _Bufs, gz) -> None:
         """The dense-parameter gradients, needed only by the dense Adam at the end of the
@@ -1211,7 +1215,7 @@ class FusedCTRTrainer:
         H1, H2, W = b.h1.shape[1], b.h2.shape[1], b.dx.shape[1]
         if side is not None:
             side.wait_event(b.ev_head)
-        with torch.cuda.stream(side) if side is not None else _nullctx():
+        with torch.cuda.stream(side) if side is not None else contextlib.nullcontext():
             jobs = [(b.fm.loss_elem.view(B, 1), None, b.loss, 1.0 / B)]  # batch mean BCE
             if "bias" in gv:  # DeepFM's FM bias: sum gz
                 jobs.append((gz.view(B, 1), None, gv["bias"].view(1)))
