@@ -499,14 +499,6 @@ static void afm_dispatch_kr(int K, Fn&& f) {
     f(std::integral_constant<int, 128>{});
 }
 
-template <typename KernelT>
-static int afm_allow_lds(KernelT kernel, size_t lds) {
-  if (lds > 64 * 1024)
-    CTR_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(kernel),
-                                      hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-  return CTR_OK;
-}
-
 extern "C" int64_t ctr_afm_workspace_bytes(int64_t B, int F, int K, int A) {
   if (B < 0 || F < 2 || F > kAfmMaxF || K < 1 || K > kAfmMaxK || A < 1 || A > kAfmMaxA) return 0;
   return align_up((int64_t)kAfmMaxBlocks * ((int64_t)A * K + A + 1) * (int64_t)sizeof(float), 16);
@@ -541,7 +533,7 @@ extern "C" int ctr_afm_forward(const void* idx, int idx_type, int64_t B, int F, 
       dispatch_bool(idx_type == CTR_IDX_I64, [&](auto i64) {
         using IdxT = std::conditional_t<decltype(i64)::value, int64_t, int32_t>;
         auto kernel = afm_forward_kernel<IdxT, KR, FULL>;
-        rc = afm_allow_lds(kernel, lds);
+        rc = allow_lds(kernel, lds);
         if (rc != CTR_OK) return;
         hipLaunchKernelGGL(kernel, grid, nt, lds, st, static_cast<const IdxT*>(idx), B, F, K, A,
                            V, emb, W1, b1, w2, b2, vec, drop, thr, scale, seed, pooled, ldp, attn,
@@ -597,7 +589,7 @@ extern "C" int ctr_afm_backward(const void* idx, int idx_type, int64_t B, int F,
           dispatch_bool(idx_type == CTR_IDX_I64, [&](auto i64) {
             using IdxT = std::conditional_t<decltype(i64)::value, int64_t, int32_t>;
             auto kernel = afm_backward_kernel<IdxT, KR, FULL, NT>;
-            rc = afm_allow_lds(kernel, lds);
+            rc = allow_lds(kernel, lds);
             if (rc != CTR_OK) return;
             hipLaunchKernelGGL(kernel, (unsigned)nblk, kAfmBwdThreads, lds, st,
                                static_cast<const IdxT*>(idx), B, F, K, A, V, emb, W1, b1, w2,

@@ -48,6 +48,17 @@ inline hipStream_t as_stream(ctr_stream_t s) { return reinterpret_cast<hipStream
 inline int64_t ceil_div(int64_t a, int64_t b) { return (a + b - 1) / b; }
 inline int64_t align_up(int64_t a, int64_t b) { return ceil_div(a, b) * b; }
 
+// A block's dynamic LDS past 64 KB (gfx950 has 160 KB per workgroup) is asked for, per
+// kernel, before the launch that needs it: a launcher that admits such a size calls this
+// first and returns its error.
+template <typename KernelT>
+inline int allow_lds(KernelT kernel, size_t lds) {
+  if (lds > 64 * 1024)
+    CTR_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(kernel),
+                                      hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+  return CTR_OK;
+}
+
 // ------------------------------------------------------------- template dispatch ------
 // The row kernels are instantiated per width (float4 columns or lanes of a row: K/4 in
 // {1, 2, 4, ..., 64}). A launcher writes its launch once, in a generic lambda that takes the
@@ -102,11 +113,14 @@ __device__ __forceinline__ void stage_rows_wave(const IdxT* __restrict__ idx, in
                                                 const float* __restrict__ emb, float* tile,
                                                 int ld, float* __restrict__ flat,
                                                 int32_t* err, int lane) {
-  // F <= 64, K % 4 == 0, F*K <= 2048 (the CTR shapes: 26 x 64, 22 x 64 ...): float4 pieces,
-  // all of a lane's (<= 8) loads in flight before the first LDS store — the loop below, not
-  // unrolled, waits for each load before its store (one memory round trip per 64 elements)
+  // F <= 64, K % 4 == 0, F*K <= 2048 (the CTR shapes: 26 x 64, 22 x 64 ...) and a 16-byte
+  // aligned table (a wave-uniform test; a contiguous view may start at any float): float4
+  // pieces, all of a lane's (<= 8) loads in flight before the first LDS store — the loop
+  // below, not unrolled, waits for each load before its store (one memory round trip per 64
+  // elements)
   constexpr int kMaxV4 = 8;
-  if (F <= 64 && (K & 3) == 0 && F * K <= 4 * 64 * kMaxV4) {
+  if (F <= 64 && (K & 3) == 0 && F * K <= 4 * 64 * kMaxV4 &&
+      (reinterpret_cast<uintptr_t>(emb) & 15) == 0) {
     const int K4 = K >> 2, n4 = F * K4;
     const long long my_row = lane < F ? (long long)load_row(idx, b * F + lane, V, err) : 0ll;
     const bool fvec = flat && (reinterpret_cast<uintptr_t>(flat) & 15) == 0;

@@ -578,14 +578,16 @@ extern "C" int ctr_feature_embedding_forward_planes(const void* idx, int idx_typ
   uint16_t* xpl = out_planes ? static_cast<uint16_t*>(out_planes->data) : nullptr;
   const int64_t xld = out_planes ? out_planes->ld : 0;
   const int64_t xps = out_planes ? out_planes->plane_stride : 0;
-  if (idx_type == CTR_IDX_I64)
-    hipLaunchKernelGGL(feature_embedding_kernel<int64_t>, grid, 256, lds, st,
-                       static_cast<const int64_t*>(idx), B, F, K, V, emb, out, err_flag, xpl,
-                       xld, xps);
-  else
-    hipLaunchKernelGGL(feature_embedding_kernel<int32_t>, grid, 256, lds, st,
-                       static_cast<const int32_t*>(idx), B, F, K, V, emb, out, err_flag, xpl,
-                       xld, xps);
+  int rc = CTR_OK;
+  dispatch_bool(idx_type == CTR_IDX_I64, [&](auto i64) {
+    using IdxT = std::conditional_t<decltype(i64)::value, int64_t, int32_t>;
+    auto kernel = feature_embedding_kernel<IdxT>;
+    rc = allow_lds(kernel, lds);  // past 64 KB the block's LDS is asked for first
+    if (rc != CTR_OK) return;
+    hipLaunchKernelGGL(kernel, grid, 256, lds, st, static_cast<const IdxT*>(idx), B, F, K, V, emb,
+                       out, err_flag, xpl, xld, xps);
+  });
+  if (rc != CTR_OK) return rc;
   CTR_LAUNCH_CHECK("ctr_feature_embedding_forward");
   return CTR_OK;
 }

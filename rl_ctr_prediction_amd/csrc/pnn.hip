@@ -279,8 +279,12 @@ __global__ __launch_bounds__(256) void ipnn_backward_sreg(const IdxT* __restrict
 // (the accumulator's initial value) and runs 16 k-steps of two fields each. Lane l holds
 // A = D[l & 31][2i + (l >> 5)] (gathered from the pair row of dcat) and B = E[2i + (l >> 5)]
 // [32 nb + (l & 31)] (the rows' 128-B halves). The products accumulate inside the matrix
-// core, so the sums are not in the LDS / register walks' order (within fp32 rounding of
-// them; tests/test_gpu_kernels.py) — the same result for every run and launch shape.
+// core, so the sums are not in the LDS / register walks' order (within 1e-5 of the L1 norm
+// of each element's summands around float64; tests/test_gpu_pair_inputs.py) — the same
+// result for every run and launch shape.
+// Known difference, finite embeddings assumed: the product multiplies D's zero diagonal by
+// e_f, a term the walks skip, so an infinite or NaN value in e_f gives NaN in slot f's own
+// gradient where the walks give a finite number.
 typedef float pnnf32x16 __attribute__((ext_vector_type(16)));
 
 template <typename IdxT>
@@ -346,44 +350,73 @@ using namespace ctr;
 // (one column per lane), the LDS-tile kernel beyond. CTR_IPNN_BWD=lds / reg / sreg / m forces
 // one (A/B runs and the tests: the three walks are bitwise one another, the product within
 // fp32 rounding of them).
-template <typename IdxT>
-static bool launch_ipnn_backward_reg(const IdxT* idx, int64_t B, int F, int K, int64_t V,
-                                     const float* emb, const float* dcat, int64_t ldd,
-                                     float* dslot, hipStream_t st) {
+enum IpnnBwd { kBwdMfma, kBwdSreg, kBwdReg, kBwdLds };
+
+static IpnnBwd ipnn_backward_pick(int F, int K) {
   const char* env = getenv("CTR_IPNN_BWD");
   const char e = env ? env[0] : '\0';
-  const unsigned grid = (unsigned)ceil_div(B, 4);
-  if ((e == '\0' || e == 'm') && F <= 32 && K % 32 == 0) {  // the matrix-core product
-    hipLaunchKernelGGL((ipnn_backward_mfma<IdxT>), grid, 256, 0, st, idx, B, F, K, V, emb, dcat,
-                       ldd, dslot);
-    return true;
-  }
-  if (e == 'l' || F > 32 || K > 64) return false;
-  if (e != 'r') {  // the scalar-operand walk
-    if (F == 26) {
-      hipLaunchKernelGGL((ipnn_backward_sreg<IdxT, 26>), grid, 256, 0, st, idx, B, K, V, emb,
-                         dcat, ldd, dslot);
-      return true;
-    }
-    if (F == 22) {
-      hipLaunchKernelGGL((ipnn_backward_sreg<IdxT, 22>), grid, 256, 0, st, idx, B, K, V, emb,
-                         dcat, ldd, dslot);
-      return true;
-    }
-  }
-  constexpr int FM = 32;
-  hipLaunchKernelGGL((ipnn_backward_reg<IdxT, FM, 1>), (unsigned)ceil_div(B, 4), 256,
-                     4 * (FM * (FM - 1) / 2) * sizeof(float), st, idx, B, F, K, V, emb, dcat,
-                     ldd, dslot);
-  return true;
+  if ((e == '\0' || e == 'm') && F <= 32 && K % 32 == 0) return kBwdMfma;
+  if (e == 'l' || F > 32 || K > 64) return kBwdLds;
+  if (e != 'r' && (F == 26 || F == 22)) return kBwdSreg;
+  return kBwdReg;
 }
 
+constexpr int kBwdRegFmax = 32;  // the register walk's field count (its pair slice in LDS)
+
+// dynamic LDS of a block (4 waves) of the kernel that is launched: the tile kernel's rows
+// and pair values, the register walk's pair values, none for the other two
+static size_t ipnn_backward_lds(IpnnBwd which, int F, int K) {
+  if (which == kBwdLds)
+    return 4 * ((size_t)F * (K + 1) + (size_t)F * (F - 1) / 2) * sizeof(float);
+  if (which == kBwdReg) return 4 * (kBwdRegFmax * (kBwdRegFmax - 1) / 2) * sizeof(float);
+  return 0;
+}
+
+template <typename IdxT>
+static int launch_ipnn_backward(IpnnBwd which, size_t lds, const IdxT* idx, int64_t B, int F,
+                                int K, int64_t V, const float* emb, const float* dcat,
+                                int64_t ldd, float* dslot, hipStream_t st) {
+  const unsigned grid = (unsigned)ceil_div(B, 4);
+  if (which == kBwdMfma) {
+    hipLaunchKernelGGL((ipnn_backward_mfma<IdxT>), grid, 256, 0, st, idx, B, F, K, V, emb, dcat,
+                       ldd, dslot);
+  } else if (which == kBwdSreg && F == 26) {
+    hipLaunchKernelGGL((ipnn_backward_sreg<IdxT, 26>), grid, 256, 0, st, idx, B, K, V, emb,
+                       dcat, ldd, dslot);
+  } else if (which == kBwdSreg) {
+    hipLaunchKernelGGL((ipnn_backward_sreg<IdxT, 22>), grid, 256, 0, st, idx, B, K, V, emb,
+                       dcat, ldd, dslot);
+  } else if (which == kBwdReg) {
+    hipLaunchKernelGGL((ipnn_backward_reg<IdxT, kBwdRegFmax, 1>), grid, 256, lds, st, idx, B, F,
+                       K, V, emb, dcat, ldd, dslot);
+  } else {
+    auto kernel = ipnn_backward_kernel<IdxT>;
+    const int rc = allow_lds(kernel, lds);
+    if (rc != CTR_OK) return rc;
+    hipLaunchKernelGGL(kernel, grid, 256, lds, st, idx, B, F, K, V, emb, dcat, ldd, dslot);
+  }
+  return CTR_OK;
+}
+
+template <typename IdxT>
+static int launch_ipnn_forward(size_t lds, const IdxT* idx, int64_t B, int F, int K, int64_t V,
+                               const float* emb, float* cat, int64_t ldc, int32_t* err,
+                               uint16_t* xpl, int64_t xld, int64_t xps, hipStream_t st) {
+  auto kernel = ipnn_forward_kernel<IdxT>;
+  const int rc = allow_lds(kernel, lds);
+  if (rc != CTR_OK) return rc;
+  hipLaunchKernelGGL(kernel, (unsigned)ceil_div(B, 4), 256, lds, st, idx, B, F, K, V, emb, cat,
+                     ldc, err, xpl, xld, xps);
+  return CTR_OK;
+}
+
+// lds: the dynamic LDS of a block of the kernel that will be launched
 static int ipnn_check(const void* idx, int idx_type, int64_t B, int F, int K, int64_t V,
-                      size_t per_wave_floats) {
+                      size_t lds) {
   CTR_REQUIRE(idx, "ipnn: null ids");
   CTR_REQUIRE(B >= 0 && F > 1 && K > 0 && V > 0, "ipnn: bad sizes");
   CTR_REQUIRE(idx_type == CTR_IDX_I32 || idx_type == CTR_IDX_I64, "bad idx_type %d", idx_type);
-  CTR_REQUIRE(4 * per_wave_floats * sizeof(float) <= 160 * 1024, "ipnn: F*K too large for LDS");
+  CTR_REQUIRE(lds <= 160 * 1024, "ipnn: F*K too large for LDS");
   return CTR_OK;
 }
 
@@ -391,8 +424,8 @@ extern "C" int ctr_ipnn_forward_planes(const void* idx, int idx_type, int64_t B,
                                        int64_t V, const float* emb, float* cat, int64_t ldc,
                                        const ctr_planes* cat_planes, int32_t* err_flag,
                                        ctr_stream_t stream) {
-  const size_t per_wave = (size_t)F * (K % 4 == 0 ? K + 4 : K + 1);
-  int rc = ipnn_check(idx, idx_type, B, F, K, V, per_wave);
+  const size_t lds = 4 * (size_t)F * (K % 4 == 0 ? K + 4 : K + 1) * sizeof(float);
+  int rc = ipnn_check(idx, idx_type, B, F, K, V, lds);
   if (rc != CTR_OK) return rc;
   const int64_t W = (int64_t)F * K + F * (F - 1) / 2;
   CTR_REQUIRE(emb && (cat || cat_planes) && (!cat || ldc >= W),
@@ -405,17 +438,13 @@ extern "C" int ctr_ipnn_forward_planes(const void* idx, int idx_type, int64_t B,
   uint16_t* xpl = cat_planes ? static_cast<uint16_t*>(cat_planes->data) : nullptr;
   const int64_t xld = cat_planes ? cat_planes->ld : 0;
   const int64_t xps = cat_planes ? cat_planes->plane_stride : 0;
-  const size_t lds = 4 * per_wave * sizeof(float);
-  const unsigned grid = (unsigned)ceil_div(B, 4);
   hipStream_t st = as_stream(stream);
-  if (idx_type == CTR_IDX_I64)
-    hipLaunchKernelGGL(ipnn_forward_kernel<int64_t>, grid, 256, lds, st,
-                       static_cast<const int64_t*>(idx), B, F, K, V, emb, cat, ldc, err_flag,
-                       xpl, xld, xps);
-  else
-    hipLaunchKernelGGL(ipnn_forward_kernel<int32_t>, grid, 256, lds, st,
-                       static_cast<const int32_t*>(idx), B, F, K, V, emb, cat, ldc, err_flag,
-                       xpl, xld, xps);
+  rc = idx_type == CTR_IDX_I64
+      ? launch_ipnn_forward(lds, static_cast<const int64_t*>(idx), B, F, K, V, emb, cat, ldc,
+                            err_flag, xpl, xld, xps, st)
+      : launch_ipnn_forward(lds, static_cast<const int32_t*>(idx), B, F, K, V, emb, cat, ldc,
+                            err_flag, xpl, xld, xps, st);
+  if (rc != CTR_OK) return rc;
   CTR_LAUNCH_CHECK("ctr_ipnn_forward");
   return CTR_OK;
 }
@@ -431,28 +460,22 @@ extern "C" int ctr_ipnn_forward(const void* idx, int idx_type, int64_t B, int F,
 extern "C" int ctr_ipnn_backward(const void* idx, int idx_type, int64_t B, int F, int K,
                                  int64_t V, const float* emb, const float* dcat, int64_t ldd,
                                  float* dslot, ctr_stream_t stream) {
-  const size_t per_wave = (size_t)F * (K + 1) + (size_t)F * (F - 1) / 2;
-  int rc = ipnn_check(idx, idx_type, B, F, K, V, per_wave);
+  // the LDS check is that of the kernel that is launched: only the tile kernel's grows with
+  // the shape
+  const IpnnBwd which = ipnn_backward_pick(F, K);
+  const size_t lds = ipnn_backward_lds(which, F, K);
+  int rc = ipnn_check(idx, idx_type, B, F, K, V, lds);
   if (rc != CTR_OK) return rc;
   CTR_REQUIRE(emb && dcat && dslot && ldd >= (int64_t)F * K + F * (F - 1) / 2,
               "ctr_ipnn_backward: bad arguments");
   if (B == 0) return CTR_OK;
-  const size_t lds = 4 * per_wave * sizeof(float);
-  const unsigned grid = (unsigned)ceil_div(B, 4);
   hipStream_t st = as_stream(stream);
-  const bool reg = idx_type == CTR_IDX_I64
-      ? launch_ipnn_backward_reg(static_cast<const int64_t*>(idx), B, F, K, V, emb, dcat, ldd,
-                                 dslot, st)
-      : launch_ipnn_backward_reg(static_cast<const int32_t*>(idx), B, F, K, V, emb, dcat, ldd,
-                                 dslot, st);
-  if (!reg) {
-    if (idx_type == CTR_IDX_I64)
-      hipLaunchKernelGGL(ipnn_backward_kernel<int64_t>, grid, 256, lds, st,
-                         static_cast<const int64_t*>(idx), B, F, K, V, emb, dcat, ldd, dslot);
-    else
-      hipLaunchKernelGGL(ipnn_backward_kernel<int32_t>, grid, 256, lds, st,
-                         static_cast<const int32_t*>(idx), B, F, K, V, emb, dcat, ldd, dslot);
-  }
+  rc = idx_type == CTR_IDX_I64
+      ? launch_ipnn_backward(which, lds, static_cast<const int64_t*>(idx), B, F, K, V, emb, dcat,
+                             ldd, dslot, st)
+      : launch_ipnn_backward(which, lds, static_cast<const int32_t*>(idx), B, F, K, V, emb, dcat,
+                             ldd, dslot, st);
+  if (rc != CTR_OK) return rc;
   CTR_LAUNCH_CHECK("ctr_ipnn_backward");
   return CTR_OK;
 }

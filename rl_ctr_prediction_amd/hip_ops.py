@@ -1288,6 +1288,10 @@ def ipnn_backward(idx: torch.Tensor, emb: torch.Tensor, dcat: torch.Tensor,
         raise ValueError("ipnn_backward: dcat must be [B, F*K + F(F-1)/2]")
     if out is None:
         out = torch.empty(B * F, K, dtype=torch.float32, device=emb.device)
+    else:
+        _f32(out, "out")
+        if out.numel() < B * F * K:
+            raise ValueError(f"ipnn_backward: out must hold [{B * F}, {K}]")
     lib.ctr_ipnn_backward(_p(idx), it, B, F, K, V, _p(emb), _p(dcat), dcat.stride(0), _p(out),
                           _stream())
     return out

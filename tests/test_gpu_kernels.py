@@ -426,6 +426,7 @@ def test_feature_embedding_vs_golden(cuda, golden):
 
 @pytest.mark.parametrize("F,K", [(2, 1), (26, 64), (22, 128), (5, 3)])
 def test_feature_embedding_vs_oracle(cuda, F, K):
+    """The path edges of the kernel are in tests/test_gpu_pair_inputs.py."""
     H = _hip()
     g = torch.Generator().manual_seed(F * K)
     V, B = 300, 45
@@ -442,7 +443,9 @@ def test_feature_embedding_vs_oracle(cuda, F, K):
 def test_ipnn_forward_and_backward_vs_oracle(cuda, F, K, B):
     """cat = flat(E[x]) ++ pair dots (p_model.py:187-195) and the per-slot gradient
     through it, against the oracle's torch-CPU ops (autograd for the backward). Flat part
-    bit-exact; dots and gradients within 1e-5 of their L1 scale (sum of |terms|)."""
+    bit-exact; dots and gradients within 1e-5 of their L1 scale (sum of |terms|). The
+    edges of the dispatch (staging paths, LDS strides and sizes, each backward kernel, both
+    id types) are in tests/test_gpu_pair_inputs.py."""
     H = _hip()
     g = torch.Generator().manual_seed(F * K + B)
     V = 300
@@ -477,7 +480,9 @@ def test_ipnn_planes_and_register_backward_bitwise(cuda, F, K, B, monkeypatch):
     forward, bit for bit (with and without the fp32 copy); the register backward (F <= 32,
     K <= 64; CTR_IPNN_BWD=reg) and the scalar-operand walk (sreg, F = 26 / 22) == the
     LDS-tile backward (CTR_IPNN_BWD=lds), bit for bit; the default (the matrix-core product
-    where F <= 32 and K % 32 == 0) == it within fp32 rounding, bitwise elsewhere."""
+    where F <= 32 and K % 32 == 0) == it within fp32 rounding, bitwise elsewhere. The path
+    edges, the documented order and the per-element bar of the product are in
+    tests/test_gpu_pair_inputs.py."""
     H = _hip()
     g = torch.Generator().manual_seed(F + 7 * K + B)
     V = 500
