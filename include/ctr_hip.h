@@ -795,6 +795,50 @@ int ctr_afm_backward(const void* idx, int idx_type, int64_t B, int F, int K, int
                      float* dw2, float* db2, void* ws, int64_t ws_bytes, int32_t* err_flag,
                      ctr_stream_t stream);
 
+/* ctr_afm_forward_step / ctr_afm_backward_step: the two entry points above with a dropout seed
+ * that advances inside a replayed HIP graph. step_ptr (device int32, may be NULL) is read
+ * once by the kernel as t, and
+ *   seed_eff = seed + (uint64_t)(uint32_t)t * 0x9E3779B97F4A7C15   (mod 2^64)
+ * stands wherever the plain entry points use seed: the call at step t is bit for bit the plain
+ * call with seed_eff, which the host can compute. NULL: seed_eff = seed (the plain entry points
+ * are these with NULL). Every other contract is the plain entry points'. */
+int ctr_afm_forward_step(const void* idx, int idx_type, int64_t B, int F, int K, int A,
+                         int64_t V, const float* emb, const float* W1, const float* b1,
+                         const float* w2, const float* b2, float drop_p, uint64_t seed,
+                         const int32_t* step_ptr, float* pooled, int64_t ldp, float* attn,
+                         int32_t* err_flag, ctr_stream_t stream);
+int ctr_afm_backward_step(const void* idx, int idx_type, int64_t B, int F, int K, int A,
+                          int64_t V, const float* emb, const float* W1, const float* b1,
+                          const float* w2, const float* b2, float drop_p, uint64_t seed,
+                          const int32_t* step_ptr, const float* attn, const float* dpooled,
+                          int64_t ldg, float* dslot, float* dW1, float* db1, float* dw2,
+                          float* db2, void* ws, int64_t ws_bytes, int32_t* err_flag,
+                          ctr_stream_t stream);
+
+/* ctr_afm_head: AFM's out head for the fused training step (p_model.py:483-486 and the BCE
+ * loss), everything between ctr_afm_forward and ctr_afm_backward in one launch. Per example b:
+ *   z_lr = bias[0] + (lin[x_b0] + lin[x_b1] + ...)      in the order of ctr_lr_forward
+ *   z    = z_lr + (<pooled_b, fc_w> + fc_b[0])          the dot in the order of ctr_deepfm_head
+ *   p, loss_elem, gz                                    the BCE head (ctr_bce_sigmoid, mean_div)
+ *   dpooled[b, k] = gz[b] * fc_w[k]                     one fp32 multiply
+ * z, p, loss_elem and gz are the bits of ctr_deepfm_head(h = pooled, w_out = fc_w, b_out = fc_b,
+ * z_fm = the z of ctr_lr_forward, labels, mean_div, drop_scale = 1). The dropout mask of the
+ * pooled vector is applied inside ctr_afm_backward, not here.
+ * Contracts:
+ *   - 2 <= F <= 64, 1 <= K <= 128, V >= 1, mean_div > 0; pooled [B, K] has row stride ldp,
+ *     dpooled [B, K] row stride ldg; z, p and loss_elem may be NULL (not written). Anything
+ *     else, a null required pointer or ldp / ldg < K returns CTR_ERR_INVALID before any HIP
+ *     call. B == 0 launches nothing.
+ *   - Ids outside [0, V) read row 0 and raise CTR_EFLAG_INDEX.
+ *   - Every access is a 4-byte one: no alignment is asked of any pointer, and none changes a
+ *     result. A row's outputs depend on that row alone; no atomics on floats.
+ *   - A wave holds 64 / G rows, G = the power of two >= F, at least 16. */
+int ctr_afm_head(const void* idx, int idx_type, int64_t B, int F, int K, int64_t V,
+                 const float* lin, const float* bias, const float* pooled, int64_t ldp,
+                 const float* fc_w, const float* fc_b, const float* labels, float mean_div,
+                 float* z, float* p, float* loss_elem, float* gz, float* dpooled, int64_t ldg,
+                 int32_t* err_flag, ctr_stream_t stream);
+
 /* ------------------------------------- Prioritized replay memory (hybrid TD3, PER) ------
  * The reference's Memory (Hybrid_TD3_model_PER.py:22-109) with storage and sampling on the
  * device: memory [N, T] and prio [N] (the [N, 1] priority column) are fp32, contiguous, and
@@ -1341,6 +1385,16 @@ typedef struct ctr_afm_bwd_args {
   void* ws; int64_t ws_bytes; int32_t* err_flag;
 } ctr_afm_bwd_args;
 int ctr_op_afm_bwd(const ctr_afm_bwd_args* a, ctr_stream_t stream);
+
+/* ctr_afm_head with its arguments in a struct (the flat entry point's contract). */
+typedef struct ctr_afm_head_args {
+  const void* idx; int idx_type; int64_t B; int F; int K; int64_t V;
+  const float* lin; const float* bias; const float* pooled; int64_t ldp;
+  const float* fc_w; const float* fc_b; const float* labels; float mean_div;
+  float* z; float* p; float* loss_elem; float* gz; float* dpooled; int64_t ldg;
+  int32_t* err_flag;
+} ctr_afm_head_args;
+int ctr_op_afm_head(const ctr_afm_head_args* a, ctr_stream_t stream);
 
 /* Wide&Deep — ctr_wd_forward / ctr_wd_embedding_grad / ctr_wd_embedding_grad_adam with their
  * arguments in a struct (the flat entry points' contract; ws sized by

@@ -6,6 +6,7 @@ reference's construction API,
 running on hand-written gfx950 HIP kernels behind the C ABI in include/ctr_hip.h
 (libctr_hip.so). See DESIGN.md.
 """
+from .afm_trainer import FusedAFMTrainer
 from .feature_embedding import Feature_Embedding
 from .ffm_trainer import FusedFFMTrainer
 from .hybrid_td3_model_per import Critic, Hybrid_TD3_Model, hybrid_actors
@@ -18,5 +19,5 @@ from .sharded import ShardedCTRTrainer
 from .trainer import FusedCTRTrainer
 
 __all__ = ["LR", "FM", "FFM", "WideAndDeep", "DeepFM", "InnerPNN", "OuterPNN", "FNN", "DCN", "AFM", "Feature_Embedding", "Net", "PolicyGradient", "FusedCTRTrainer",
-           "FusedFFMTrainer", "ShardedCTRTrainer", "DenseAdam", "PrioritizedMemory",
+           "FusedFFMTrainer", "FusedAFMTrainer", "ShardedCTRTrainer", "DenseAdam", "PrioritizedMemory",
            "Hybrid_TD3_Model", "Critic", "hybrid_actors", "DeviceMetrics", "roc_auc_score"]

@@ -244,6 +244,13 @@ class AfmBwdArgs(C.Structure):
                         ("ws_bytes", _i64), ("err_flag", _vp)]
 
 
+class AfmHeadArgs(C.Structure):
+    _fields_ = _IDXF + [("lin", _vp), ("bias", _vp), ("pooled", _vp), ("ldp", _i64),
+                        ("fc_w", _vp), ("fc_b", _vp), ("labels", _vp), ("mean_div", _f32),
+                        ("z", _vp), ("p", _vp), ("loss_elem", _vp), ("gz", _vp),
+                        ("dpooled", _vp), ("ldg", _i64), ("err_flag", _vp)]
+
+
 class WdFwdArgs(C.Structure):
     _fields_ = _IDXF + [("emb", _vp), ("lin", _vp), ("bias", _vp), ("flat", _vp), ("ldf", _i64),
                         ("x_planes", _planes_p), ("z_lin", _vp), ("err_flag", _vp)]
@@ -279,7 +286,8 @@ OP_ARGS = {"fm_fwd": FmFwdArgs, "fm_bwd": FmBwdArgs, "deepfm_gather_concat": Dee
            "grad_clip_scale": GradClipScaleArgs, "td3v10_store": Td3v10StoreArgs,
            "td3v10_keys": Td3v10KeysArgs, "td3v10_sample": Td3v10SampleArgs,
            "td3v10_update": Td3v10UpdateArgs, "bn_eval_backward": BnEvalBackwardArgs,
-           "afm_fwd": AfmFwdArgs, "afm_bwd": AfmBwdArgs, "wd_fwd": WdFwdArgs,
+           "afm_fwd": AfmFwdArgs, "afm_bwd": AfmBwdArgs, "afm_head": AfmHeadArgs,
+           "wd_fwd": WdFwdArgs,
            "wd_embedding_grad": WdEmbeddingGradArgs,
            "wd_embedding_grad_adam": WdEmbeddingGradAdamArgs}
 
@@ -411,6 +419,13 @@ SIGNATURES = {
     "ctr_afm_backward": (_i32, [_vp, _i32, _i64, _i32, _i32, _i32, _i64, _vp, _vp, _vp, _vp, _vp,
                                 _f32, _u64, _vp, _vp, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _i64,
                                 _vp, _vp]),
+    "ctr_afm_forward_step": (_i32, [_vp, _i32, _i64, _i32, _i32, _i32, _i64, _vp, _vp, _vp, _vp,
+                                    _vp, _f32, _u64, _vp, _vp, _i64, _vp, _vp, _vp]),
+    "ctr_afm_backward_step": (_i32, [_vp, _i32, _i64, _i32, _i32, _i32, _i64, _vp, _vp, _vp, _vp,
+                                     _vp, _f32, _u64, _vp, _vp, _vp, _i64, _vp, _vp, _vp, _vp,
+                                     _vp, _vp, _i64, _vp, _vp]),
+    "ctr_afm_head": (_i32, [_vp, _i32, _i64, _i32, _i32, _i64, _vp, _vp, _vp, _i64, _vp, _vp, _vp,
+                            _f32, _vp, _vp, _vp, _vp, _vp, _i64, _vp, _vp]),
     "ctr_dcn_cross_workspace_bytes": (_i64, [_i64, _i32, _i32]),
     "ctr_dcn_cross_forward": (_i32, [_i64, _i32, _i32, _vp, _i64, _vp, _vp, _vp, _vp, _vp, _i64,
                                      _vp, _vp]),

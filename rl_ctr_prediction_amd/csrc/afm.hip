@@ -159,15 +159,24 @@ __device__ __forceinline__ float afm_keep(uint64_t seed, uint64_t ctr, uint32_t 
   return hash_u32(seed, ctr) >= thr ? scale : 0.f;
 }
 
+// The dropout seed of a step: seed + t * the splitmix64 increment (mod 2^64), t = *step_ptr read
+// once as an unsigned 32-bit value — a seed the host can compute, so the _step entry points at
+// step t are the plain ones called with it. NULL: the seed itself. A captured graph replays
+// the pointer, not the value: every replay draws the masks of its own step.
+__device__ __forceinline__ uint64_t afm_step_seed(uint64_t seed, const int32_t* step_ptr) {
+  return step_ptr ? seed + (uint64_t)(uint32_t)step_ptr[0] * 0x9E3779B97F4A7C15ull : seed;
+}
+
 // ------------------------------------------------------------------- forward ----------
 template <typename IdxT, int KR, bool FULL>
 __global__ __launch_bounds__(afm_fwd_threads(KR)) void afm_forward_kernel(
     const IdxT* __restrict__ idx, int64_t B, int F, int K, int A, int64_t V,
     const float* __restrict__ emb, const float* __restrict__ W1, const float* __restrict__ b1,
     const float* __restrict__ w2, const float* __restrict__ b2, int vec, int drop, uint32_t thr,
-    float scale, uint64_t seed, float* __restrict__ pooled, int64_t ldp,
-    float* __restrict__ attn, int32_t* err) {
+    float scale, uint64_t seed, const int32_t* __restrict__ step_ptr,
+    float* __restrict__ pooled, int64_t ldp, float* __restrict__ attn, int32_t* err) {
   extern __shared__ __attribute__((aligned(16))) unsigned char afm_lds[];
+  seed = afm_step_seed(seed, step_ptr);
   const int P = afm_pairs(F), lde = afm_lde(K);
   const int tid = threadIdx.x, nt = blockDim.x;
   long long* rows = reinterpret_cast<long long*>(afm_lds);
@@ -238,10 +247,12 @@ __global__ __launch_bounds__(kAfmBwdThreads) void afm_backward_kernel(
     const IdxT* __restrict__ idx, int64_t B, int F, int K, int A, int64_t V,
     const float* __restrict__ emb, const float* __restrict__ W1, const float* __restrict__ b1,
     const float* __restrict__ w2, int vec_emb, int vec_w, int vec_out, int drop, uint32_t thr,
-    float scale, uint64_t seed, const float* __restrict__ attn,
-    const float* __restrict__ dpooled, int64_t ldg, float* __restrict__ dslot,
-    float* __restrict__ pT, float* __restrict__ pS, float* __restrict__ pD, int32_t* err) {
+    float scale, uint64_t seed, const int32_t* __restrict__ step_ptr,
+    const float* __restrict__ attn, const float* __restrict__ dpooled, int64_t ldg,
+    float* __restrict__ dslot, float* __restrict__ pT, float* __restrict__ pS,
+    float* __restrict__ pD, int32_t* err) {
   extern __shared__ __attribute__((aligned(16))) unsigned char afm_lds[];
+  seed = afm_step_seed(seed, step_ptr);
   const int P = afm_pairs(F), lde = afm_lde(K), AW = (A + 31) / 32;
   const int tid = threadIdx.x;
   constexpr int nt = kAfmBwdThreads;
@@ -504,15 +515,15 @@ extern "C" int64_t ctr_afm_workspace_bytes(int64_t B, int F, int K, int A) {
   return align_up((int64_t)kAfmMaxBlocks * ((int64_t)A * K + A + 1) * (int64_t)sizeof(float), 16);
 }
 
-extern "C" int ctr_afm_forward(const void* idx, int idx_type, int64_t B, int F, int K, int A,
-                               int64_t V, const float* emb, const float* W1, const float* b1,
-                               const float* w2, const float* b2, float drop_p, uint64_t seed,
-                               float* pooled, int64_t ldp, float* attn, int32_t* err_flag,
-                               ctr_stream_t stream) {
-  int rc = afm_check("ctr_afm_forward", idx, idx_type, B, F, K, A, V, emb, W1, b1, w2, b2, drop_p);
+static int afm_forward_impl(const char* who, const void* idx, int idx_type, int64_t B, int F,
+                            int K, int A, int64_t V, const float* emb, const float* W1,
+                            const float* b1, const float* w2, const float* b2, float drop_p,
+                            uint64_t seed, const int32_t* step_ptr, float* pooled, int64_t ldp,
+                            float* attn, int32_t* err_flag, ctr_stream_t stream) {
+  int rc = afm_check(who, idx, idx_type, B, F, K, A, V, emb, W1, b1, w2, b2, drop_p);
   if (rc != CTR_OK) return rc;
-  CTR_REQUIRE(pooled || B == 0, "ctr_afm_forward: null pooled");
-  CTR_REQUIRE(ldp >= K, "ctr_afm_forward: ldp %lld < K = %d", (long long)ldp, K);
+  CTR_REQUIRE(pooled || B == 0, "%s: null pooled", who);
+  CTR_REQUIRE(ldp >= K, "%s: ldp %lld < K = %d", who, (long long)ldp, K);
   if (B == 0) return CTR_OK;
   const int P = afm_pairs(F);
   const int64_t want = ceil_div(P, kWave) * kWave;  // one thread per pair, whole waves
@@ -536,32 +547,49 @@ extern "C" int ctr_afm_forward(const void* idx, int idx_type, int64_t B, int F, 
         rc = allow_lds(kernel, lds);
         if (rc != CTR_OK) return;
         hipLaunchKernelGGL(kernel, grid, nt, lds, st, static_cast<const IdxT*>(idx), B, F, K, A,
-                           V, emb, W1, b1, w2, b2, vec, drop, thr, scale, seed, pooled, ldp, attn,
-                           err_flag);
+                           V, emb, W1, b1, w2, b2, vec, drop, thr, scale, seed, step_ptr, pooled,
+                           ldp, attn, err_flag);
       });
     });
   });
   if (rc != CTR_OK) return rc;
-  CTR_LAUNCH_CHECK("ctr_afm_forward");
+  CTR_LAUNCH_CHECK(who);
   return CTR_OK;
 }
 
-extern "C" int ctr_afm_backward(const void* idx, int idx_type, int64_t B, int F, int K, int A,
-                                int64_t V, const float* emb, const float* W1, const float* b1,
-                                const float* w2, const float* b2, float drop_p, uint64_t seed,
-                                const float* attn, const float* dpooled, int64_t ldg,
-                                float* dslot, float* dW1, float* db1, float* dw2, float* db2,
-                                void* ws, int64_t ws_bytes, int32_t* err_flag,
-                                ctr_stream_t stream) {
-  int rc =
-      afm_check("ctr_afm_backward", idx, idx_type, B, F, K, A, V, emb, W1, b1, w2, b2, drop_p);
+extern "C" int ctr_afm_forward(const void* idx, int idx_type, int64_t B, int F, int K, int A,
+                               int64_t V, const float* emb, const float* W1, const float* b1,
+                               const float* w2, const float* b2, float drop_p, uint64_t seed,
+                               float* pooled, int64_t ldp, float* attn, int32_t* err_flag,
+                               ctr_stream_t stream) {
+  return afm_forward_impl("ctr_afm_forward", idx, idx_type, B, F, K, A, V, emb, W1, b1, w2, b2,
+                          drop_p, seed, nullptr, pooled, ldp, attn, err_flag, stream);
+}
+
+extern "C" int ctr_afm_forward_step(const void* idx, int idx_type, int64_t B, int F, int K,
+                                    int A, int64_t V, const float* emb, const float* W1,
+                                    const float* b1, const float* w2, const float* b2,
+                                    float drop_p, uint64_t seed, const int32_t* step_ptr,
+                                    float* pooled, int64_t ldp, float* attn, int32_t* err_flag,
+                                    ctr_stream_t stream) {
+  return afm_forward_impl("ctr_afm_forward_step", idx, idx_type, B, F, K, A, V, emb, W1, b1, w2,
+                          b2, drop_p, seed, step_ptr, pooled, ldp, attn, err_flag, stream);
+}
+
+static int afm_backward_impl(const char* who, const void* idx, int idx_type, int64_t B, int F,
+                             int K, int A, int64_t V, const float* emb, const float* W1,
+                             const float* b1, const float* w2, const float* b2, float drop_p,
+                             uint64_t seed, const int32_t* step_ptr, const float* attn,
+                             const float* dpooled, int64_t ldg, float* dslot, float* dW1,
+                             float* db1, float* dw2, float* db2, void* ws, int64_t ws_bytes,
+                             int32_t* err_flag, ctr_stream_t stream) {
+  int rc = afm_check(who, idx, idx_type, B, F, K, A, V, emb, W1, b1, w2, b2, drop_p);
   if (rc != CTR_OK) return rc;
-  CTR_REQUIRE((attn && dpooled && dslot) || B == 0,
-              "ctr_afm_backward: null attn / dpooled / dslot");
-  CTR_REQUIRE(dW1 && db1 && dw2 && db2, "ctr_afm_backward: null dW1 / db1 / dw2 / db2");
-  CTR_REQUIRE(ldg >= K, "ctr_afm_backward: ldg %lld < K = %d", (long long)ldg, K);
+  CTR_REQUIRE((attn && dpooled && dslot) || B == 0, "%s: null attn / dpooled / dslot", who);
+  CTR_REQUIRE(dW1 && db1 && dw2 && db2, "%s: null dW1 / db1 / dw2 / db2", who);
+  CTR_REQUIRE(ldg >= K, "%s: ldg %lld < K = %d", who, (long long)ldg, K);
   const int64_t need = ctr_afm_workspace_bytes(B, F, K, A);
-  CTR_REQUIRE(ws && ws_bytes >= need, "ctr_afm_backward: workspace %lld < %lld bytes",
+  CTR_REQUIRE(ws && ws_bytes >= need, "%s: workspace %lld < %lld bytes", who,
               (long long)ws_bytes, (long long)need);
   hipStream_t st = as_stream(stream);
   float* pT = static_cast<float*>(ws);
@@ -593,18 +621,43 @@ extern "C" int ctr_afm_backward(const void* idx, int idx_type, int64_t B, int F,
             if (rc != CTR_OK) return;
             hipLaunchKernelGGL(kernel, (unsigned)nblk, kAfmBwdThreads, lds, st,
                                static_cast<const IdxT*>(idx), B, F, K, A, V, emb, W1, b1, w2,
-                               vec_emb, vec_w, vec_out, drop, thr, scale, seed, attn, dpooled,
-                               ldg, dslot, pT, pS, pD, err_flag);
+                               vec_emb, vec_w, vec_out, drop, thr, scale, seed, step_ptr, attn,
+                               dpooled, ldg, dslot, pT, pS, pD, err_flag);
           });
         });
       });
     });
     if (rc != CTR_OK) return rc;
-    CTR_LAUNCH_CHECK("ctr_afm_backward");
+    CTR_LAUNCH_CHECK(who);
   }
   // nblk == 0 (B == 0): the sums are empty, the outputs zero
   hipLaunchKernelGGL(afm_backward_finalize, (unsigned)A, kAfmMaxK, 0, st, K, A, nblk, pT, pS, pD,
                      W1, b1, w2, dW1, db1, dw2, db2);
   CTR_LAUNCH_CHECK("ctr_afm_backward (finalize)");
   return CTR_OK;
+}
+
+extern "C" int ctr_afm_backward(const void* idx, int idx_type, int64_t B, int F, int K, int A,
+                                int64_t V, const float* emb, const float* W1, const float* b1,
+                                const float* w2, const float* b2, float drop_p, uint64_t seed,
+                                const float* attn, const float* dpooled, int64_t ldg,
+                                float* dslot, float* dW1, float* db1, float* dw2, float* db2,
+                                void* ws, int64_t ws_bytes, int32_t* err_flag,
+                                ctr_stream_t stream) {
+  return afm_backward_impl("ctr_afm_backward", idx, idx_type, B, F, K, A, V, emb, W1, b1, w2, b2,
+                           drop_p, seed, nullptr, attn, dpooled, ldg, dslot, dW1, db1, dw2, db2,
+                           ws, ws_bytes, err_flag, stream);
+}
+
+extern "C" int ctr_afm_backward_step(const void* idx, int idx_type, int64_t B, int F, int K,
+                                     int A, int64_t V, const float* emb, const float* W1,
+                                     const float* b1, const float* w2, const float* b2,
+                                     float drop_p, uint64_t seed, const int32_t* step_ptr,
+                                     const float* attn, const float* dpooled, int64_t ldg,
+                                     float* dslot, float* dW1, float* db1, float* dw2,
+                                     float* db2, void* ws, int64_t ws_bytes, int32_t* err_flag,
+                                     ctr_stream_t stream) {
+  return afm_backward_impl("ctr_afm_backward_step", idx, idx_type, B, F, K, A, V, emb, W1, b1,
+                           w2, b2, drop_p, seed, step_ptr, attn, dpooled, ldg, dslot, dW1, db1,
+                           dw2, db2, ws, ws_bytes, err_flag, stream);
 }

@@ -10,6 +10,7 @@
 // rows per instruction. All F row loads of an example are issued before the first use
 // (register staging), the per-k sums over fields are xor-butterflies (ds_bpermute/DPP).
 #include "ctr_common.h"
+#include "head_dot.h"
 
 namespace ctr {
 
@@ -252,15 +253,7 @@ __global__ __launch_bounds__(256) void deepfm_head_kernel(
   float hv[kMaxJ], wv[kMaxJ];
   float part = 0.f;
   if (held) {
-#pragma unroll
-    for (int q = 0; q < kMaxJ; ++q) {
-      const int j = lane + q * kWave;
-      hv[q] = j < H ? hb[j] : 0.f;
-      wv[q] = j < H ? w[j] : 0.f;
-    }
-#pragma unroll
-    for (int q = 0; q < kMaxJ; ++q)
-      if (lane + q * kWave < H) part += hv[q] * wv[q];
+    part = head_lane_dot<kMaxJ>(hb, w, H, lane, hv, wv);  // shared with ctr_afm_head
   } else {
     for (int j = lane; j < H; j += kWave) part += hb[j] * w[j];
   }

@@ -246,6 +246,13 @@ extern "C" int ctr_op_afm_bwd(const ctr_afm_bwd_args* a, ctr_stream_t stream) {
                           a->err_flag, stream);
 }
 
+extern "C" int ctr_op_afm_head(const ctr_afm_head_args* a, ctr_stream_t stream) {
+  CTR_REQUIRE(a, "ctr_op_afm_head: null args");
+  return ctr_afm_head(a->idx, a->idx_type, a->B, a->F, a->K, a->V, a->lin, a->bias, a->pooled,
+                      a->ldp, a->fc_w, a->fc_b, a->labels, a->mean_div, a->z, a->p, a->loss_elem,
+                      a->gz, a->dpooled, a->ldg, a->err_flag, stream);
+}
+
 extern "C" int ctr_op_wd_fwd(const ctr_wd_fwd_args* a, ctr_stream_t stream) {
   CTR_REQUIRE(a, "ctr_op_wd_fwd: null args");
   return ctr_wd_forward(a->idx, a->idx_type, a->B, a->F, a->K, a->V, a->emb, a->lin, a->bias,

@@ -25,6 +25,7 @@ __all__ = [
     "fm_embedding_grad_adam", "segment_sum_rows_adam",
     "rows_to_dense", "adam_dense", "fm_step_tail", "adam_embedding", "adam_scalars", "feature_embedding",
     "dcn_cross_forward", "dcn_cross_backward", "afm_forward", "afm_backward",
+    "afm_head", "afm_step_seed",
     "wd_forward", "wd_embedding_grad", "wd_embedding_grad_adam",
     "AFM_BWD_MAX_BLOCKS",
     "lr_forward", "ensemble_preds", "ensemble_preds_ex", "per_store_step",
@@ -1451,11 +1452,13 @@ def _afm_params(W1, b1, w2, b2, K):
 def afm_forward(idx: torch.Tensor, emb: torch.Tensor, W1: torch.Tensor, b1: torch.Tensor,
                 w2: torch.Tensor, b2: torch.Tensor, drop_p: float = 0.0, seed: int = 0,
                 want_attn: bool = True, out: torch.Tensor | None = None,
-                attn: torch.Tensor | None = None, err_flag=None):
+                attn: torch.Tensor | None = None, err_flag=None, step_dev=None):
     """AFM's attention pooling (p_model.py:473-482): (pooled [B, K], attn [B, F(F-1)/2] or
     None). attn is the softmax over the pairs before dropout, what afm_backward reads. Both
     dropouts (attention weights and pooled vector) use one (seed, drop_p); drop_p = 0: none.
-    out: a float32 [>= B, >= K] matrix with unit column stride (rows may be strided)."""
+    out: a float32 [>= B, >= K] matrix with unit column stride (rows may be strided).
+    step_dev (one device int32 t, read by the kernel): the masks of
+    afm_step_seed(seed, t) — a captured graph then draws new masks at every replay."""
     idx, it = _idx(idx)
     _f32(emb, "feature_embedding.weight")
     B, F = idx.shape
@@ -1472,21 +1475,33 @@ def afm_forward(idx: torch.Tensor, emb: torch.Tensor, W1: torch.Tensor, b1: torc
         _f32(attn, "attn")
         if attn.numel() < B * P:
             raise ValueError(f"afm_forward: attn must hold [{B}, {P}]")
-    lib.ctr_afm_forward(_p(idx), it, B, F, K, A, V, _p(emb), _p(W1), _p(b1), _p(w2), _p(b2),
-                        float(drop_p), int(seed) & (2**64 - 1), _p(out),
-                        out.stride(0) if B > 1 else K,  # a lone row's stride is arbitrary
-                        _p(attn), _p(err_flag), _stream())
+    ldp = out.stride(0) if B > 1 else K  # a lone row's stride is arbitrary
+    if step_dev is None:
+        lib.ctr_afm_forward(_p(idx), it, B, F, K, A, V, _p(emb), _p(W1), _p(b1), _p(w2), _p(b2),
+                            float(drop_p), int(seed) & (2**64 - 1), _p(out), ldp, _p(attn),
+                            _p(err_flag), _stream())
+    else:
+        _i32(step_dev, "step_dev", 1)
+        lib.ctr_afm_forward_step(_p(idx), it, B, F, K, A, V, _p(emb), _p(W1), _p(b1), _p(w2),
+                                 _p(b2), float(drop_p), int(seed) & (2**64 - 1), _p(step_dev),
+                                 _p(out), ldp, _p(attn), _p(err_flag), _stream())
     return (out if out.shape == (B, K) else out[:B, :K]), attn
+
+
+def afm_step_seed(seed: int, step: int) -> int:
+    """The dropout seed ctr_afm_forward_step / ctr_afm_backward_step use at device step
+    `step`: seed + uint32(step) * 0x9E3779B97F4A7C15 mod 2^64."""
+    return (int(seed) + (int(step) & 0xFFFFFFFF) * 0x9E3779B97F4A7C15) & (2**64 - 1)
 
 
 def afm_backward(idx: torch.Tensor, emb: torch.Tensor, W1: torch.Tensor, b1: torch.Tensor,
                  w2: torch.Tensor, b2: torch.Tensor, attn: torch.Tensor, dpooled: torch.Tensor,
                  drop_p: float = 0.0, seed: int = 0, out: dict | None = None,
-                 err_flag=None) -> dict:
+                 err_flag=None, step_dev=None) -> dict:
     """Backward of afm_forward from dL/dpooled [B, K] and the forward's attn: dict(dslot
-    [B*F, K] in slot order, dW1 [A, K], db1 [A], dw2 [A], db2 [1]); (seed, drop_p) as in the
-    forward. One kernel over the batch plus the deterministic reduction of its per-block
-    partials."""
+    [B*F, K] in slot order, dW1 [A, K], db1 [A], dw2 [A], db2 [1]); (seed, drop_p, step_dev)
+    as in the forward. One kernel over the batch plus the deterministic reduction of its
+    per-block partials."""
     idx, it = _idx(idx)
     _f32(emb, "feature_embedding.weight")
     B, F = idx.shape
@@ -1505,11 +1520,57 @@ def afm_backward(idx: torch.Tensor, emb: torch.Tensor, W1: torch.Tensor, b1: tor
         if out[name].numel() < n:
             raise ValueError(f"afm_backward: {name} must hold {n} values")
     ws = Workspace.get(lib.ctr_afm_workspace_bytes(B, F, K, A), emb.device)
-    lib.ctr_afm_backward(_p(idx), it, B, F, K, A, V, _p(emb), _p(W1), _p(b1), _p(w2), _p(b2),
-                         float(drop_p), int(seed) & (2**64 - 1), _p(attn), _p(dpooled),
-                         dpooled.stride(0) if B > 1 else K,
-                         _p(out["dslot"]), _p(out["dW1"]), _p(out["db1"]), _p(out["dw2"]),
-                         _p(out["db2"]), _p(ws), ws.numel(), _p(err_flag), _stream())
+    head = (_p(idx), it, B, F, K, A, V, _p(emb), _p(W1), _p(b1), _p(w2), _p(b2), float(drop_p),
+            int(seed) & (2**64 - 1))
+    tail = (_p(attn), _p(dpooled), dpooled.stride(0) if B > 1 else K, _p(out["dslot"]),
+            _p(out["dW1"]), _p(out["db1"]), _p(out["dw2"]), _p(out["db2"]), _p(ws), ws.numel(),
+            _p(err_flag), _stream())
+    if step_dev is None:
+        lib.ctr_afm_backward(*head, *tail)
+    else:
+        _i32(step_dev, "step_dev", 1)
+        lib.ctr_afm_backward_step(*head, _p(step_dev), *tail)
+    return out
+
+
+def afm_head(idx: torch.Tensor, lin: torch.Tensor, bias: torch.Tensor, pooled: torch.Tensor,
+             fc_w: torch.Tensor, fc_b: torch.Tensor, labels: torch.Tensor,
+             mean_div: float | None = None, out: dict | None = None, err_flag=None) -> dict:
+    """AFM's out head for the fused step in one launch (ctr_afm_head): z = (bias + sum_f
+    lin[x_f]) + fc(pooled), the BCE head and dpooled = gz * fc_w — dict(z, p, loss_elem, gz [B],
+    dpooled [B, K]); z, p, loss_elem, gz are the bits of deepfm_head(pooled, fc_w, fc_b,
+    lr_forward(idx, lin, bias)["z"], labels, mean_div). pooled and out["dpooled"]: float32
+    [>= B, >= K] with unit column stride (rows may be strided). out: the five buffers (z, p,
+    loss_elem may be None), so a captured graph allocates nothing."""
+    idx, it = _idx(idx)
+    if idx.dim() != 2:
+        raise ValueError("afm_head: idx must be [B, F]")
+    B, F = idx.shape
+    _f32(lin, "linear.weight")
+    _f32(bias, "bias")
+    _f32(fc_w, "fc.weight")
+    _f32(fc_b, "fc.bias")
+    _f32(labels, "labels")
+    K, V = fc_w.numel(), lin.numel()
+    if bias.numel() != 1 or fc_b.numel() != 1 or labels.numel() != B:
+        raise ValueError(f"afm_head: bias and fc.bias hold one value, labels B = {B}")
+    _rows2d(pooled, "pooled", B, K)
+    dev = lin.device
+    if out is None:
+        e = lambda *s: torch.empty(*s, dtype=torch.float32, device=dev)  # noqa: E731
+        out = dict(z=e(B), p=e(B), loss_elem=e(B), gz=e(B), dpooled=e(B, K))
+    for name in ("z", "p", "loss_elem", "gz"):
+        t = out.get(name)
+        if t is None and name != "gz":
+            continue
+        if _f32(t, name).numel() < B:
+            raise ValueError(f"afm_head: {name} must hold {B} values")
+    dp = _rows2d(out["dpooled"], "dpooled", B, K)
+    lib.ctr_afm_head(_p(idx), it, B, F, K, V, _p(lin), _p(bias), _p(pooled),
+                     pooled.stride(0) if B > 1 else K, _p(fc_w), _p(fc_b), _p(labels),
+                     float(B if mean_div is None else mean_div), _p(out.get("z")),
+                     _p(out.get("p")), _p(out.get("loss_elem")), _p(out["gz"]), _p(dp),
+                     dp.stride(0) if B > 1 else K, _p(err_flag), _stream())
     return out
 
 

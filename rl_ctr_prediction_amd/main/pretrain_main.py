@@ -16,7 +16,7 @@ reference:
     ``models/model_params/{campaign}FMbest.pth`` (:164-168).
 
 Same flags and defaults as the reference (:256-269). The training step is the fused HIP
-step (FM, DeepFM, W&D, IPNN, OPNN, FFM; LR, FNN, DCN and AFM: the reference's own step through autograd over the HIP kernels); batches come in file order from one device-resident copy (the reference's
+step (FM, DeepFM, W&D, IPNN, OPNN, FFM; LR, FNN, DCN and AFM: the reference's own step through autograd over the HIP kernels; AFM with ``--afm_trainer fused``: FusedAFMTrainer); batches come in file order from one device-resident copy (the reference's
 DataLoader without shuffle).
 """
 from __future__ import annotations
@@ -69,9 +69,10 @@ def build_model(model_name, feature_nums, field_nums, latent_dims):
 
 def main(data_path, dataset_name, campaign_id, valid_day, test_day, latent_dims, model_name, epoch,
          learning_rate, weight_decay, early_stop_type, batch_size, device, save_param_dir,
-         verbose=True, metrics="host"):
+         verbose=True, metrics="host", afm_trainer="autograd"):
     if metrics not in ("host", "device"):
         raise ValueError(f"metrics={metrics!r}: expected 'host' or 'device'")
+    fused_afm = _pm._check_afm_trainer(afm_trainer)
     if not os.path.exists(save_param_dir + campaign_id):
         os.mkdir(save_param_dir + campaign_id)
     device = torch.device(device)
@@ -87,7 +88,7 @@ def main(data_path, dataset_name, campaign_id, valid_day, test_day, latent_dims,
                                map_location=device, weights_only=True)
         model.load_embedding(fm_params)
     loss = nn.BCELoss()
-    trainer = make_trainer(model_name, model, learning_rate, weight_decay)
+    trainer = make_trainer(model_name, model, learning_rate, weight_decay, fused_afm=fused_afm)
 
     valid_aucs, valid_losses, history = [], [], []
     early_stop_index, is_early_stop = 0, False
@@ -166,6 +167,8 @@ def _parser():
     parser.add_argument("--save_param_dir", default="../models/model_params/")
     parser.add_argument("--metrics", default="host", choices=["host", "device"],
                         help="where AUC and validation loss are computed")
+    parser.add_argument("--afm_trainer", default="autograd", choices=["autograd", "fused"],
+                        help="AFM's training step: AutogradTrainer or FusedAFMTrainer")
     return parser
 
 
@@ -175,4 +178,4 @@ if __name__ == "__main__":
     main(args.data_path, args.dataset_name, args.campaign_id, args.valid_day, args.test_day,
          args.latent_dims, args.model_name, args.epoch, args.learning_rate, args.weight_decay,
          args.early_stop_type, args.batch_size, args.device, args.save_param_dir,
-         metrics=args.metrics)
+         metrics=args.metrics, afm_trainer=args.afm_trainer)

@@ -12,7 +12,9 @@ of the checkpoint four epochs back.
 Differences, all deliberate: the training step is the fused HIP step (FM, DeepFM, W&D, IPNN
 and OPNN; FFM: FusedFFMTrainer, the same deferred-exact Adam over its F*V field-table rows;
 LR, FNN, DCN and AFM: AutogradTrainer, the reference's own step — autograd over the HIP
-kernels and torch.optim.Adam — which also serves the other models for comparison; all ten
+kernels and torch.optim.Adam — which also serves the other models for comparison; AFM with
+``--afm_trainer fused``: FusedAFMTrainer, the sparse, deferred-exact, graph-captured step
+(``autograd`` stays the default); all ten
 families of the reference's p_model.py are built: main() builds its model through
 build_model, get_model itself keeps refusing W&D and AFM); the batches are
 sliced from one device-resident copy of the data instead of 8 DataLoader worker
@@ -35,6 +37,7 @@ from sklearn.metrics import roc_auc_score
 from . import creat_data as Data
 from .binfmt import load_encoded
 from . import p_model as Model
+from .afm_trainer import FusedAFMTrainer
 from .ffm_trainer import FusedFFMTrainer
 from .metrics import DeviceMetrics
 from .trainer import FusedCTRTrainer
@@ -82,9 +85,12 @@ def build_model(model_name, feature_nums, field_nums, latent_dims, fallback=None
     return (fallback or get_model)(model_name, feature_nums, field_nums, latent_dims)
 
 
-def make_trainer(model_name, model, learning_rate, weight_decay):
+def make_trainer(model_name, model, learning_rate, weight_decay, fused_afm=False):
     """The training step of a model family: the fused HIP step where one exists (FM, DeepFM,
-    W&D, IPNN, OPNN; FFM), else the reference's own step through autograd (LR, FNN, DCN, AFM)."""
+    W&D, IPNN, OPNN; FFM), else the reference's own step through autograd (LR, FNN, DCN, AFM).
+    fused_afm: AFM through FusedAFMTrainer instead (the drivers' ``--afm_trainer fused``)."""
+    if model_name == "AFM" and fused_afm:
+        return FusedAFMTrainer(model, lr=learning_rate, weight_decay=weight_decay)
     if model_name == "FFM":
         return FusedFFMTrainer(model, lr=learning_rate, weight_decay=weight_decay)
     if model_name in ("LR", "FNN", "DCN", "AFM"):
@@ -215,6 +221,12 @@ def _check_metrics(metrics):
     return metrics == "device"
 
 
+def _check_afm_trainer(afm_trainer):
+    if afm_trainer not in ("autograd", "fused"):
+        raise ValueError(f"afm_trainer={afm_trainer!r}: expected 'autograd' or 'fused'")
+    return afm_trainer == "fused"
+
+
 def _predict_device(model, data_loader, keep_predictions=False):
     """The device counterpart of _predict: every batch goes to a DeviceMetrics accumulator
     (one launch, no .item() / .tolist()), compute() reads the results once. Returns its dict
@@ -269,12 +281,14 @@ def eva_stopping(valid_aucs, valid_losses, type):  # noqa: A002 (reference name)
 
 def main(data_path, dataset_name, campaign_id, latent_dims, model_name, epoch, learning_rate,
          weight_decay, early_stop_type, batch_size, device, save_param_dir, verbose=True,
-         _epoch_fn=None, metrics="host"):
+         _epoch_fn=None, metrics="host", afm_trainer="autograd"):
     """metrics: "host" (the reference's evaluation loop, the default) or "device"
-    (DeviceMetrics: no host read per batch).
+    (DeviceMetrics: no host read per batch). afm_trainer: "autograd" (the default) or "fused"
+    (FusedAFMTrainer), AFM's training step; other families ignore it.
     _epoch_fn(model, trainer, train_fm, loss, device, batch_size) -> mean train loss: the
     epoch loop of a driver variant (pretrain_main_2's slicing loop); default: DeviceBatches."""
     _check_metrics(metrics)
+    fused_afm = _check_afm_trainer(afm_trainer)
     if not os.path.exists(save_param_dir + campaign_id):
         os.mkdir(save_param_dir + campaign_id)
     device = torch.device(device)
@@ -288,7 +302,7 @@ def main(data_path, dataset_name, campaign_id, latent_dims, model_name, epoch, l
 
     model = build_model(model_name, feature_nums, field_nums, latent_dims).to(device)
     loss = nn.BCELoss()
-    trainer = make_trainer(model_name, model, learning_rate, weight_decay)
+    trainer = make_trainer(model_name, model, learning_rate, weight_decay, fused_afm=fused_afm)
 
     valid_aucs, valid_losses, history = [], [], []
     early_stop_index, is_early_stop = 0, False
@@ -361,6 +375,8 @@ def _parser():
     parser.add_argument("--save_param_dir", default="../models/model_params/")
     parser.add_argument("--metrics", default="host", choices=["host", "device"],
                         help="where AUC and validation loss are computed")
+    parser.add_argument("--afm_trainer", default="autograd", choices=["autograd", "fused"],
+                        help="AFM's training step: AutogradTrainer or FusedAFMTrainer")
     return parser
 
 
@@ -369,4 +385,5 @@ if __name__ == "__main__":
     setup_seed(1)
     main(args.data_path, args.dataset_name, args.campaign_id, args.latent_dims, args.model_name,
          args.epoch, args.learning_rate, args.weight_decay, args.early_stop_type,
-         args.batch_size, args.device, args.save_param_dir, metrics=args.metrics)
+         args.batch_size, args.device, args.save_param_dir, metrics=args.metrics,
+         afm_trainer=args.afm_trainer)

@@ -44,7 +44,7 @@ def train(model, optimizer, train_data, loss, device, len_train, batch):
 
 def main(data_path, dataset_name, campaign_id, latent_dims, model_name, epoch, learning_rate,
          weight_decay, early_stop_type, batch_size, device, save_param_dir, verbose=True,
-         metrics="host"):
+         metrics="host", afm_trainer="autograd"):
     cache = {}
 
     def epoch_fn(model, trainer, train_fm, loss, dev, bs):
@@ -55,7 +55,8 @@ def main(data_path, dataset_name, campaign_id, latent_dims, model_name, epoch, l
 
     return _pm.main(data_path, dataset_name, campaign_id, latent_dims, model_name, epoch,
                     learning_rate, weight_decay, early_stop_type, batch_size, device,
-                    save_param_dir, verbose=verbose, _epoch_fn=epoch_fn, metrics=metrics)
+                    save_param_dir, verbose=verbose, _epoch_fn=epoch_fn, metrics=metrics,
+                    afm_trainer=afm_trainer)
 
 
 if __name__ == "__main__":
@@ -63,4 +64,5 @@ if __name__ == "__main__":
     setup_seed(1)
     main(args.data_path, args.dataset_name, args.campaign_id, args.latent_dims, args.model_name,
          args.epoch, args.learning_rate, args.weight_decay, args.early_stop_type,
-         args.batch_size, args.device, args.save_param_dir, metrics=args.metrics)
+         args.batch_size, args.device, args.save_param_dir, metrics=args.metrics,
+         afm_trainer=args.afm_trainer)
