@@ -17,12 +17,12 @@ contiguous [F*V, K] buffer (same Parameter objects, same state_dict), so the F*V
   linear: per-row sums of dL/dz    + its deferred Adam; bias: sum(dL/dz) + dense Adam
 
 No dense [F*V, K] gradient is materialised (the AutogradTrainer path writes F dense [V, K]
-gradients and streams F*V*K*24 B of Adam traffic per step). Single-process steps are
-captured into HIP graphs and replayed, as in FusedCTRTrainer.step.
+gradients and streams F*V*K*24 B of Adam traffic per step). The step bookkeeping, the
+optimiser interface and the capture / replay of the step as a HIP graph are StepTrainer's
+(step_trainer.py); this module holds FFM's tables and launch sequence.
 """
 from __future__ import annotations
 
-import os
 from dataclasses import dataclass
 
 import torch
@@ -30,7 +30,7 @@ import torch.nn as nn
 
 from . import hip_ops
 from .p_model import FFM
-from .trainer import flush_hooks, graph_capture, live_pool
+from .step_trainer import StepTrainer
 
 
 @dataclass
@@ -47,26 +47,24 @@ class _FFMBufs:
     loss: torch.Tensor                 # [1]
 
 
-class FusedFFMTrainer:
+class FusedFFMTrainer(StepTrainer):
     """Fused forward + BCE + backward + deferred-exact dense Adam for FFM.
 
-    Args mirror ``torch.optim.Adam(model.parameters(), lr, betas, eps, weight_decay)``;
-    the interface is FusedCTRTrainer's (step / flush / reset_optimizer /
-    optimizer_state_dict / check_errors)."""
+    Args mirror ``torch.optim.Adam(model.parameters(), lr, betas, eps, weight_decay)``; the
+    interface (step / flush / reset_optimizer / optimizer_state_dict / check_errors), the
+    step bookkeeping and the graph replay are StepTrainer's."""
+
+    NAME = "FusedFFMTrainer"
 
     def __init__(self, model: nn.Module, lr: float = 1e-3, weight_decay: float = 0.0,
                  betas=(0.9, 0.999), eps: float = 1e-8, seed: int | None = None):
         if not isinstance(model, FFM):
             raise TypeError("FusedFFMTrainer drives FFM")
         tabs = [e.weight for e in model.field_feature_embeddings]
-        self.model = model
         self.kind = "FFM"
-        self.lr, self.weight_decay, self.betas, self.eps = float(lr), float(weight_decay), betas, eps
-        self.device = tabs[0].device
-        if self.device.type != "cuda":
-            raise RuntimeError("FusedFFMTrainer needs the model on a ROCm device")
         self.F = len(tabs)
         self.V, self.K = tabs[0].shape
+        super().__init__(model, tabs[0].device, self.K, lr, weight_decay, betas, eps, seed)
         if self.F < 2:
             raise ValueError("FusedFFMTrainer: FFM needs at least 2 fields")
         if self.F * self.V >= 2**31:
@@ -91,44 +89,6 @@ class FusedFFMTrainer:
         self.m_b = torch.zeros_like(self.bias)
         self.v_b = torch.zeros_like(self.bias)
         self.ptrs = model._ptrs.get(tabs)
-        self._vec_ok = K % 4 == 0 and 64 % (K // 4 or 1) == 0 and K <= 256
-        self.fuse_apply = os.environ.get("CTR_FUSE_APPLY", "1") != "0"
-        self.keep_grads = False  # fused apply: keep every row's sum in b.grad_rows (tests)
-        self.step_ctr = torch.tensor([0, 1], dtype=torch.int32, device=dev)
-        self.step_done, self.step_cur = self.step_ctr[0:1], self.step_ctr[1:2]
-        self.step_table = hip_ops.AdamStepTable(self.lr, self.betas, dev)
-        self.err = torch.zeros(1, dtype=torch.int32, device=dev)
-        self.loss_sum = torch.zeros(1, dtype=torch.float64, device=dev)
-        # own scratch and capture stream (hip_ops.Workspace: no captured graph shares
-        # scratch with another object's launches)
-        self._scratch = hip_ops.Workspace()
-        self._capture_stream = torch.cuda.Stream(device=dev)
-        self.step_count = 0
-        self._dirty = False
-        flush_hooks(model, self)
-        self._bufs: _FFMBufs | None = None
-        self._bufsets: dict = {}
-        self.seed = int(torch.initial_seed() if seed is None else seed) & (2**63 - 1)
-        self.use_graphs = True
-        self.max_graphs = 8
-        self._graphs: dict = {}
-        # every batch is copied into the fixed input buffers of its shape (ids, labels), so
-        # one captured graph per shape serves a stream of fresh batches
-        self._inputs: dict = {}
-        self.captures = 0
-        # bounded staleness, as FusedCTRTrainer.flush_every
-        self.flush_every = int(os.environ.get("CTR_FLUSH_EVERY", "32"))
-        self._flushed_at = 0
-        self._graph_pool = torch.cuda.graph_pool_handle()
-        self._graph_tab_version = self.step_table.version
-        self.timing = None  # FusedCTRTrainer's bench hook: not instrumented here
-
-    def __del__(self):
-        try:  # a captured graph must not be destroyed while it still runs
-            if getattr(self, "_graphs", None):
-                torch.cuda.synchronize(self.device)
-        except Exception:  # interpreter shutdown
-            pass
 
     # ----------------------------------------------------------------- optimiser -----
     def _table_args(self):
@@ -137,50 +97,19 @@ class FusedFFMTrainer:
     def _w_args(self):
         return (self.w, self.m_w, self.v_w, None, None, None, self.last_w)
 
-    def flush(self) -> None:
-        """Bring every row of every table up to the last completed step."""
-        self._flushed_at = self.step_count
-        if self._dirty and self.step_count > 0:
-            for tab in (self._table_args(), self._w_args()):
-                hip_ops.adam_deferred_flush(*tab, self.step_count, self.step_table, self.betas,
-                                            self.eps, self.weight_decay)
-        self._dirty = False
+    def _tables(self):
+        return (self._table_args(), self._w_args())
 
-    def reset_optimizer(self, lr: float | None = None) -> None:
-        """A re-created torch.optim.Adam (all_main/pretrain_main.py:153), optionally at a new
-        learning rate; captured graphs stay valid (the step table is rewritten in place)."""
-        self.flush()
-        if lr is not None:
-            self.lr = float(lr)
-            self.step_table.set_lr(self.lr)
-        for t in (self.m_T, self.v_T, self.m_w, self.v_w, self.m_b, self.v_b, self.last_T,
-                  self.last_w):
-            t.zero_()
-        self.step_ctr.copy_(torch.tensor([0, 1], dtype=torch.int32))
-        self.step_count = 0
-        self._flushed_at = 0
+    def _dense_moments(self):
+        return (self.m_b, self.v_b)
 
-    def optimizer_state_dict(self) -> dict:
-        """torch.optim.Adam-compatible state_dict: parameter i is the i-th entry of
-        model.named_parameters() (for FFM: bias first — a root module's own parameters come
-        before its submodules' —, then linear.weight and the field tables)."""
-        self.flush()
+    def _moments(self) -> dict:
         V = self.V
         moments = {"bias": (self.m_b, self.v_b), "linear.weight": (self.m_w, self.v_w)}
         for t in range(self.F):
             sl = slice(t * V, (t + 1) * V)
             moments[f"field_feature_embeddings.{t}.weight"] = (self.m_T[sl], self.v_T[sl])
-        named = [n for n, _ in self.model.named_parameters()]
-        state = {i: {"step": torch.tensor(float(self.step_count)),
-                     "exp_avg": moments[n][0].clone(), "exp_avg_sq": moments[n][1].clone()}
-                 for i, n in enumerate(named)}
-        return {"state": state if self.step_count else {},
-                "param_groups": [{"lr": self.lr, "betas": self.betas, "eps": self.eps,
-                                  "weight_decay": self.weight_decay, "amsgrad": False,
-                                  "params": list(range(len(named)))}]}
-
-    def check_errors(self) -> None:
-        hip_ops.check_index_error(self.err)
+        return moments
 
     # --------------------------------------------------------------------- buffers ---
     def _buffers(self, B: int, F: int) -> _FFMBufs:
@@ -199,83 +128,12 @@ class FusedFFMTrainer:
         return b
 
     # ------------------------------------------------------------------------ step ----
-    def step(self, x: torch.Tensor, y: torch.Tensor, return_loss: bool = True):
-        """One training step on batch (x [B,F] int64/int32, y [B] 0/1); returns the mean
-        BCE as a fresh 1-element device tensor (no host sync), or None with
-        return_loss=False. Every step adds its loss to ``loss_sum`` (float64, on the device;
-        read_loss_sum / reset_loss_sum, as FusedCTRTrainer)."""
-        with self._scratch.scope():
-            loss = self._step(x, y)
-            return loss.clone() if return_loss else None
-
-    def reset_loss_sum(self) -> None:
-        self.loss_sum.zero_()
-
-    def read_loss_sum(self) -> float:
-        return float(self.loss_sum.item())
-
-    def _step(self, x: torch.Tensor, y: torch.Tensor) -> torch.Tensor:
-        B, F = x.shape
-        if F != self.F:
-            raise ValueError(f"FusedFFMTrainer: batch has {F} fields, model {self.F}")
-        if self._flush_due():
-            self.flush()
-        if self.use_graphs:
-            return self._graph_step(x, y)
-        self.step_table.ensure(self.step_count + 1)
-        loss = self._launch(x, y)
-        self._after_step()
-        return loss
-
-    def _flush_due(self) -> bool:
-        """True when `flush_every` steps have passed since the last flush."""
-        return self.flush_every > 0 and self.step_count - self._flushed_at >= self.flush_every
-
-    def _after_step(self) -> None:
-        self.step_count += 1
-        self._dirty = True
-
-    def _graph_step(self, x, y):
-        if self.step_table.capacity < self.step_count + 2:
-            self.step_table.ensure(max(self.step_count + 2, 2 * self.step_table.capacity))
-        if self._graph_tab_version != self.step_table.version:
-            torch.cuda.synchronize(self.device)  # none may still run when destroyed
-            self._graphs.clear()  # they hold the old table's address
-            self._graph_tab_version = self.step_table.version
-        B, F = x.shape
-        key = (B, F, x.dtype)
-        inp = self._inputs.get(key)
-        if inp is None:
-            inp = self._inputs[key] = (torch.empty(B, F, dtype=x.dtype, device=self.device),
-                                       torch.empty(B, dtype=torch.float32, device=self.device))
-        xs, ys = inp
-        xs.copy_(x, non_blocking=True)
-        ys.copy_(y.reshape(-1), non_blocking=True)
-        hit = self._graphs.get(key)
-        if hit is None:
-            loss = self._launch(xs, ys)  # the real step; also sizes every buffer
-            self._after_step()
-            if len(self._graphs) < self.max_graphs:
-                g = torch.cuda.CUDAGraph()
-                with graph_capture(g, pool=live_pool(self), stream=self._capture_stream):
-                    self._launch(xs, ys)  # captured, not executed
-                self._graphs[key] = (g, self._bufs)
-                self.captures += 1
-            return loss
-        g, self._bufs = hit
-        g.replay()
-        self._after_step()
-        return self._bufs.loss
-
     def _launch(self, x: torch.Tensor, y: torch.Tensor) -> torch.Tensor:
         """Enqueue one step; step-dependent values come from the device step counter."""
         B, F = x.shape
         V, K = self.V, self.K
         b = self._buffers(B, F)
-        y = y.reshape(-1)
-        if y.dtype != torch.float32:
-            y = y.float()
-        y = y.contiguous()
+        y = self._float_labels(y)
         tabs = [e.weight.data for e in self.model.field_feature_embeddings]
         hint = self.step_count + 1
         opt = dict(betas=self.betas, eps=self.eps, weight_decay=self.weight_decay)

@@ -666,44 +666,29 @@ class ShardedCTRTrainer(FusedCTRTrainer):
         return xb
 
     def _sharded_graph_step(self, slot: InputSlot, mean_div: float, C: int):
-        if self.step_table.capacity < self.step_count + 2:
-            self.step_table.ensure(max(self.step_count + 2, 2 * self.step_table.capacity))
-        if self._graph_tab_version != self.step_table.version:
-            torch.cuda.synchronize(self.device)
-            self._graphs.clear()
-            self._graph_tab_version = self.step_table.version
+        self._sync_step_table()
         mlp = getattr(self.model, "mlp", None)
         drops = tuple(float(mlp[i].p) for i in (2, 5)) if mlp is not None else ()
         key = (slot.shape, slot.index, C, mean_div, self.model.training, drops)
-        hit = self._graphs.get(key)
-        if hit is None:
-            loss = self._launch_sharded(slot, mean_div, C)
-            self._after_step()
-            if len(self._graphs) < self.max_graphs:
-                g = torch.cuda.CUDAGraph()
-                # collectives inside: a thread-local capture, so the process group's
-                # watchdog thread may query its events while this thread captures
-                mode = "thread_local" if self._coll else "global"
-                try:
-                    with graph_capture(g, pool=live_pool(self), stream=self._capture_stream,
-                                       capture_error_mode=mode):
-                        self._launch_sharded(slot, mean_div, C)  # captured, not executed
-                except RuntimeError as e:  # a backend that refuses capture: eager from here
-                    if self.world_size == 1 and not self._coll:
-                        raise
-                    warnings.warn(f"ShardedCTRTrainer: step graph capture failed ({e}); "
-                                  "launching the steps eagerly")
-                    torch.cuda.synchronize(self.device)
-                    self._graph_ok = False
-                    return loss
-                self._graphs[key] = (g, self._bufs)
-                self.captures += 1
-            return loss
-        g, self._bufs = hit
-        self._bufs.plan = slot.plan
-        g.replay()
-        self._after_step()
-        return self._bufs.loss
+        # collectives inside: a thread-local capture, so the process group's watchdog
+        # thread may query its events while this thread captures
+        mode = "thread_local" if self._coll else "global"
+        done = self.step_count
+
+        def on_hit(b):
+            b.plan = slot.plan
+
+        try:
+            return self._replay_or_capture(key, lambda: self._launch_sharded(slot, mean_div, C),
+                                           on_hit, capture_error_mode=mode)
+        except RuntimeError as e:  # a backend that refuses capture: eager from here
+            if (self.world_size == 1 and not self._coll) or self.step_count == done:
+                raise  # (the step itself failed, not its capture)
+            warnings.warn(f"ShardedCTRTrainer: step graph capture failed ({e}); "
+                          "launching the steps eagerly")
+            torch.cuda.synchronize(self.device)
+            self._graph_ok = False
+            return self._bufs.loss  # the eager step's, run before the capture
 
     def _xchg(self, out: torch.Tensor, send: torch.Tensor, coll: bool) -> torch.Tensor:
         """The equal-split all-to-all of one exchange buffer into `out`, or (one process, no
@@ -898,10 +883,7 @@ class ShardedCTRTrainer(FusedCTRTrainer):
         b = self._buffers(B, F)
         if self._slot2u is None or self._slot2u.numel() < B * F:
             self._slot2u = torch.empty(B * F, dtype=torch.int32, device=self.device)
-        y = y.reshape(-1)
-        if y.dtype != torch.float32:
-            y = y.float()
-        y = y.contiguous()
+        y = self._float_labels(y)
         bias = self.views.get("bias")
         has_lin = self.w_tab is not None
         self._sync_weight_planes()

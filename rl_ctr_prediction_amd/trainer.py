@@ -23,13 +23,16 @@ Optimizer modes (identical results, bitwise — tests/test_gpu_deferred.py):
       reset_optimizer(), and by the driver at every epoch end.
   "dense": one streaming pass over all V rows every step (rowmap-gated gradients,
       24 B/element/step).
+
+The optimiser interface (flush / reset_optimizer / optimizer_state_dict), the device step
+counters and step table, and the capture / replay of step graphs are StepTrainer's
+(step_trainer.py), shared with FusedFFMTrainer and FusedAFMTrainer; this module holds the
+model kinds, the input slots with their plan lookahead, and the launch sequence.
 """
 from __future__ import annotations
 
 import contextlib
-import gc
 import os
-import weakref
 from dataclasses import dataclass
 
 import torch
@@ -38,51 +41,8 @@ import torch.nn as nn
 from . import hip_ops
 from .distributed import allgather_sparse_rows, allreduce_sum_, world
 from .p_model import FM, DeepFM, InnerPNN, OuterPNN, WideAndDeep
-
-
-@contextlib.contextmanager
-def graph_capture(g, **kw):
-    """torch.cuda.graph with Python's cyclic GC paused: a collection during the capture
-    could destroy another trainer's captured graphs (HIP calls that are illegal while a
-    stream captures -> abort)."""
-    gc.collect()  # dead cycles holding captured graphs die here, outside any capture
-    was = gc.isenabled()
-    gc.disable()
-    try:
-        with torch.cuda.graph(g, **kw):
-            yield
-    finally:
-        if was:
-            gc.enable()
-
-
-def live_pool(owner):
-    """The graph memory pool handle of `owner` (a trainer / PolicyGradient) for its next
-    capture: torch frees a shared pool once every graph captured into it is gone, and a
-    capture into the freed pool's handle trips an allocator assert (and leaves the RNG in
-    capture state), so an owner whose step graphs were all dropped starts a new pool."""
-    if not owner._graphs:
-        owner._graph_pool = torch.cuda.graph_pool_handle()
-    return owner._graph_pool
-
-
-def flush_hooks(model: nn.Module, trainer) -> None:
-    """forward / state_dict pre-hooks that flush the trainer's deferred rows, holding the
-    trainer weakly (no model <-> trainer cycle: a dropped trainer is freed at once)."""
-    ref = weakref.ref(trainer)
-
-    def flush(*_):
-        t = ref()
-        if t is not None:
-            t.flush()
-
-    def drain(*_):  # a pending weight-gradient tail is applied before the loaded values land
-        t = ref()
-        if t is not None:
-            t._drain_tail()
-    model.register_forward_pre_hook(flush)
-    model.register_state_dict_pre_hook(flush)
-    model._register_load_state_dict_pre_hook(drain)
+from .step_trainer import (StepTrainer, flush_hooks, graph_capture, live_pool,  # noqa: F401
+                           pack_dense)  # (re-exported: pg_model.py and sharded.py import them here)
 
 
 DEEPFM_DENSE = ("bias", "mlp.0.weight", "mlp.0.bias", "mlp.3.weight", "mlp.3.bias",
@@ -249,15 +209,23 @@ class _Bufs:
     xp_idx: int = 0
 
 
-class FusedCTRTrainer:
+class FusedCTRTrainer(StepTrainer):
     """Fused forward + BCE + backward + dense Adam for FM / DeepFM / WideAndDeep / the PNNs:
     the model classes of the _KINDS table, whose entries hold all that differs between them.
+    The optimiser interface and the step-graph bookkeeping are StepTrainer's; the step itself
+    (input slots, plan lookahead, the pipelined tail) is this class's own.
 
     Args mirror ``torch.optim.Adam(model.parameters(), lr, betas, eps, weight_decay)``.
     The model's dense parameters (FM bias, DeepFM MLP) are re-pointed into one flat
     buffer (same Parameter objects, same state_dict), so the dense Adam and the
     data-parallel all-reduce are one launch each.
     """
+
+    NAME = "FusedCTRTrainer"
+    # per shape at most 2 x ring-size graphs (slot x plan-built-ahead), independent of the
+    # batch count
+    MAX_GRAPHS = 24
+    _SYNC_BEFORE_DEL = ("_graphs", "_rings")  # the slots' plan graphs replay on plan streams
 
     def __init__(self, model: nn.Module, lr: float = 1e-3, weight_decay: float = 0.0,
                  betas=(0.9, 0.999), eps: float = 1e-8, process_group=None, seed: int | None = None,
@@ -266,41 +234,32 @@ class FusedCTRTrainer:
         if spec is None:
             raise TypeError("FusedCTRTrainer drives FM, DeepFM, WideAndDeep, InnerPNN or "
                             "OuterPNN")
-        self.model = model
+        if optimizer_mode not in ("deferred", "dense"):
+            raise ValueError(f"optimizer_mode must be 'deferred' or 'dense', not {optimizer_mode!r}")
         self.kind = spec.name
-        self.lr, self.weight_decay, self.betas, self.eps = float(lr), float(weight_decay), betas, eps
         self.group = process_group
         self.emb_name = embedding_name(model) + ".weight"  # its state_dict key
+        self.model = model  # _table() reads it
         E = self._table()
-        self.device = E.device
-        if self.device.type != "cuda":
-            raise RuntimeError("FusedCTRTrainer needs the model on a ROCm device")
         self.V, self.K = self._vocab_size(E), E.shape[1]
+        # every stream of this trainer has a HIP handle of its own (_new_stream): the scratch
+        # buffers of hip_ops.Workspace are per stream handle, and torch hands streams out of
+        # a 32-stream pool round-robin, so two roles could otherwise alias one stream and
+        # share scratch while running concurrently (the step graphs are captured on the
+        # trainer's own capture stream for the same reason, not on torch's global one)
+        self._own_streams: list = []
+        super().__init__(model, E.device, self.K, lr, weight_decay, betas, eps, seed,
+                         deferred=optimizer_mode == "deferred")
         self._ksum_ptr = model.ksum().data_ptr() if spec.ksum else None
-        named = dict(model.named_parameters())
         self.dense_names = spec.dense
-        # 16-B aligned views (offsets multiples of 4 floats): the GEMMs read the weights
-        # through the float4 / LDS-DMA path only when a row start is 16-B aligned
-        self.offsets, total = {}, 0
-        for n in self.dense_names:
-            self.offsets[n] = total
-            total += (named[n].numel() + 3) // 4 * 4
-        flat = torch.zeros(total, dtype=torch.float32, device=self.device)
         # the dense gradient with 4 floats of tail room: the row-sharded step all-reduces the
         # batch loss there, in the gradient's own collective (sharded.py)
-        self._grad_ext = torch.zeros(total + 4, dtype=torch.float32, device=self.device)
-        self.flat_grad = self._grad_ext[:total]
-        self.views, self.grad_views = {}, {}
-        for n in self.dense_names:
-            p, off = named[n], self.offsets[n]
-            k = p.numel()
-            flat[off:off + k].copy_(p.data.reshape(-1))
-            p.data = flat[off:off + k].view_as(p)
-            self.views[n] = p.data
-            self.grad_views[n] = self.flat_grad[off:off + k].view_as(p)
-        self.flat = flat
-        self.m_flat = torch.zeros_like(flat)
-        self.v_flat = torch.zeros_like(flat)
+        self.flat, self.flat_grad, self.offsets, self.views, self.grad_views = pack_dense(
+            dict(model.named_parameters()), spec.dense, self.device, grad_tail=4)
+        total = self.flat.numel()
+        self._grad_ext = self.flat_grad.as_strided((total + 4,), (1,))
+        self.m_flat = torch.zeros_like(self.flat)
+        self.v_flat = torch.zeros_like(self.flat)
         # the embedding rows this trainer's optimiser owns: all of them here, one shard in
         # ShardedCTRTrainer (rl_ctr_prediction_amd/sharded.py)
         self.row_lo, self.row_hi = self._table_rows()
@@ -314,28 +273,15 @@ class FusedCTRTrainer:
             self.w_tab = self._own_rows(model.linear.weight.data)
             self.m_w = torch.zeros(n_rows, dtype=torch.float32, device=self.device)
             self.v_w = torch.zeros_like(self.m_w)
-        if optimizer_mode not in ("deferred", "dense"):
-            raise ValueError(f"optimizer_mode must be 'deferred' or 'dense', not {optimizer_mode!r}")
-        self.deferred = optimizer_mode == "deferred"
         # dense mode: row -> compact gradient slot map; deferred mode: the owner scratch of
         # the plan-free catch-up (csrc/adam.hip deferred_mark_kernel)
         self.rowmap = torch.full((n_rows,), -1, dtype=torch.int32, device=self.device)
         self.last = torch.zeros(n_rows, dtype=torch.int32, device=self.device)
-        # device step counters: [0] completed steps, [1] the step in flight (ctr_step_begin/end)
-        # initialised to {0, 1}: ctr_step_end advances both, so no step-begin launch is needed
-        self.step_ctr = torch.tensor([0, 1], dtype=torch.int32, device=self.device)
-        self.step_done, self.step_cur = self.step_ctr[0:1], self.step_ctr[1:2]
-        # fused scatter + Adam apply (one process, deferred mode); keep_grads keeps every
-        # row's gradient sum in b.grad_rows / b.grad_lin (tests read them)
-        self.fuse_apply = os.environ.get("CTR_FUSE_APPLY", "1") != "0"
-        # smallest K the fused apply is used at (A/B: CTR_FUSE_APPLY_MIN_K)
-        self.fuse_apply_min_k = int(os.environ.get("CTR_FUSE_APPLY_MIN_K", "16"))
         # capture order of the step's first fork: the plan first where it is the critical
         # path (FM: the forward / backward are short; C2 31.6 vs 28.4 M ex/s), the catch-up
         # and forward first where they are (MLP kinds; C3 12.39 vs 11.67 M ex/s)
         env = os.environ.get("CTR_PLAN_FIRST")
         self.plan_first = (env == "1") if env in ("0", "1") else not spec.mlp
-        self.keep_grads = False
         # input staging (single process): every batch is copied into a fixed slot of its
         # shape (InputSlot) and the step graph of that slot is replayed, so fresh batches
         # never miss the graph cache. Plan lookahead (step(..., next_x=)): the next batches
@@ -347,7 +293,6 @@ class FusedCTRTrainer:
         self._rings: dict = {}     # (B, F, dtype) -> [InputSlot]
         self._staged: dict = {}    # ids key of a batch staged ahead -> its InputSlot
         self.max_slots = 8
-        self.captures = 0          # step graphs captured (tests: bounded, batch-independent)
         self._ev_start = None
         # lookahead (every kind): the next batches' ids are staged and planned on the plan
         # stream, so the step graph starts with no copy and no plan branch, and catches its
@@ -356,23 +301,6 @@ class FusedCTRTrainer:
         # cycled batches it had measured 12.7 vs 12.8, the in-step copies then absent)
         env = os.environ.get("CTR_PLAN_LOOKAHEAD")
         self.plan_lookahead = (env == "1") if env in ("0", "1") else True
-        # bounded staleness of deferred Adam: every `flush_every` steps all rows are brought
-        # to the current step (one tiled flush pass), so a row a batch touches has missed at
-        # most that many steps and the in-step catch-up replays stay short under a stream
-        # of fresh batches (0: only at forward / state_dict / epoch end)
-        self.flush_every = int(os.environ.get("CTR_FLUSH_EVERY", "32"))
-        self._flushed_at = 0
-        self._vec_ok = self.K % 4 == 0 and 64 % (self.K // 4 or 1) == 0 and self.K <= 256
-        # every stream of this trainer has a HIP handle of its own (_new_stream): the scratch
-        # buffers of hip_ops.Workspace are per stream handle, and torch hands streams out of
-        # a 32-stream pool round-robin, so two roles could otherwise alias one stream and
-        # share scratch while running concurrently (the step graphs are captured on the
-        # trainer's own capture stream for the same reason, not on torch's global one)
-        self._own_streams: list = []
-        # scratch owned by this trainer alone: its captured graphs reference no buffer that
-        # another object's launches use (hip_ops.Workspace)
-        self._scratch = hip_ops.Workspace()
-        self._capture_stream = self._new_stream()
         self._side = self._new_stream() if self.deferred and self._vec_ok else None
         # the weight-gradient work shares the plan's side stream (it starts after the head,
         # long after the plan is built): the captured graph then has exactly two parallel
@@ -436,37 +364,9 @@ class FusedCTRTrainer:
                       and world()[1] == 1 and env == "1")
         # (bufset, X planes, their index) of the step whose dW0 + MLP Adam is pending
         self._tail = None
-        self.step_table = hip_ops.AdamStepTable(self.lr, self.betas, self.device)
-        self._dirty = False
-        if self.deferred:  # nothing may read a table with rows still owed steps
-            flush_hooks(model, self)
-        self.err = torch.zeros(1, dtype=torch.int32, device=self.device)
-        # every step's mean loss added in float64 by its last launch (the driver's epoch sum)
-        self.loss_sum = torch.zeros(1, dtype=torch.float64, device=self.device)
-        self.step_count = 0
-        self._bufs: _Bufs | None = None
-        self._bufsets: dict = {}
-        self.seed = int(torch.initial_seed() if seed is None else seed) & (2**63 - 1)
-        # HIP-graph replay of the single-process step (see step()): per shape at most
-        # 2 x ring-size graphs (slot x plan-built-ahead), independent of the batch count
-        self.use_graphs = True
-        self.max_graphs = 24
-        self._graphs: dict = {}
-        self._graph_pool = torch.cuda.graph_pool_handle()
-        self._graph_tab_version = self.step_table.version
-        # bench hook: {"adam": [], "gather": [], ...} -> [(start, end, work)] HIP events
-        # recorded on the launch stream around those kernels; only the keys present in the
-        # dict are instrumented (each event is a queue packet: keep the timed region lean)
-        self.timing: dict | None = None
 
-    def __del__(self):
-        # a captured graph must not be destroyed while it still runs: plan-stream replays
-        # (lookahead) are not ordered before anything the caller synchronises with
-        try:
-            if getattr(self, "_graphs", None) or getattr(self, "_rings", None):
-                torch.cuda.synchronize(self.device)
-        except Exception:  # interpreter shutdown
-            pass
+    def _new_capture_stream(self):
+        return self._new_stream()
 
     def _table(self) -> nn.Parameter:
         """The model's embedding table Parameter (the one place that knows its name)."""
@@ -483,19 +383,6 @@ class FusedCTRTrainer:
         the shard)."""
         return t[self.row_lo:self.row_hi]
 
-    def _mark(self, key):
-        if self.timing is None or key not in self.timing:
-            return None
-        ev = torch.cuda.Event(enable_timing=True)
-        ev.record()
-        return ev
-
-    def _span(self, key, start, work=None):
-        if start is not None:
-            ev = torch.cuda.Event(enable_timing=True)
-            ev.record()
-            self.timing[key].append((start, ev, work))
-
     def _gemm_planes(self, a, b, a_rc, b_rc, M, N, K, **kw):
         """hip_ops.gemm_planes with a timing span carrying the product's flop count."""
         t = self._mark("gemm")
@@ -504,72 +391,14 @@ class FusedCTRTrainer:
         return out
 
     # ----------------------------------------------------------------- optimiser -----
-    def flush(self) -> None:
-        """Apply the pending weight-gradient tail (pipelined MLP kinds) and bring every
-        embedding row up to the last completed step (deferred mode): every parameter and
-        moment is then the reference's after the last step. The plan streams only read
-        staged ids and write plans: nothing to wait for."""
-        self._drain_tail()
-        self._flush_table()
+    def _tables(self):
+        return ((self.E_tab, self.m_E, self.v_E, self.w_tab, self.m_w, self.v_w, self.last),)
 
-    def _flush_table(self) -> None:
-        """The embedding rows up to the last completed step (deferred mode)."""
-        self._flushed_at = self.step_count
-        if self.deferred and self._dirty and self.step_count > 0:
-            t = self._mark("flush")
-            hip_ops.adam_deferred_flush(self.E_tab, self.m_E, self.v_E,
-                                        self.w_tab, self.m_w, self.v_w, self.last,
-                                        self.step_count, self.step_table, self.betas, self.eps,
-                                        self.weight_decay)
-            self._span("flush", t)
-        self._dirty = False
-
-    def reset_optimizer(self, lr: float | None = None) -> None:
-        """What ``torch.optim.Adam(...)`` re-created every epoch does
-        (all_main/pretrain_main.py:153): fresh moments, step 0 — with `lr`, at a new
-        learning rate (main/pretrain_main.py:180-181: ``learning_rate += 1e-4`` then a new
-        Adam): the per-step scalars are rewritten in place (captured graphs stay valid)."""
-        self.flush()
-        if lr is not None:
-            self.lr = float(lr)
-            self.step_table.set_lr(self.lr)
-        for t in (self.m_flat, self.v_flat, self.m_E, self.v_E, self.m_w, self.v_w):
-            if t is not None:
-                t.zero_()
-        self.last.zero_()
-        self.step_ctr.copy_(torch.tensor([0, 1], dtype=torch.int32))
-        self.step_count = 0
-        self._flushed_at = 0
-
-    def _bound_staleness(self) -> None:
-        """Flush once `flush_every` steps have passed since the last flush: no row is then
-        more than that many steps behind when a batch reads it."""
-        if (self.deferred and self.flush_every > 0
-                and self.step_count - self._flushed_at >= self.flush_every):
-            self._flush_table()  # the tables only: the pipelined tail stays pending
-
-    def optimizer_state_dict(self) -> dict:
-        """torch.optim.Adam-compatible state_dict (parameter order = model.parameters())."""
-        self.flush()
-        named = list(self.model.named_parameters())
-        m = {n: v for n, v in zip(self.dense_names, self._split(self.m_flat))}
-        v = {n: v for n, v in zip(self.dense_names, self._split(self.v_flat))}
-        m[self.emb_name], v[self.emb_name] = self.m_E, self.v_E
+    def _moments(self) -> dict:
+        moments = {self.emb_name: (self.m_E, self.v_E), **self._flat_moments()}
         if self.m_w is not None:
-            m["linear.weight"], v["linear.weight"] = self.m_w.view(-1, 1), self.v_w.view(-1, 1)
-        state = {i: {"step": torch.tensor(float(self.step_count)), "exp_avg": m[n].clone(),
-                     "exp_avg_sq": v[n].clone()} for i, (n, _) in enumerate(named)}
-        return {"state": state if self.step_count else {},
-                "param_groups": [{"lr": self.lr, "betas": self.betas, "eps": self.eps,
-                                  "weight_decay": self.weight_decay, "amsgrad": False,
-                                  "params": list(range(len(named)))}]}
-
-    def _split(self, flat):
-        out = []
-        for n in self.dense_names:
-            k, off = self.views[n].numel(), self.offsets[n]
-            out.append(flat[off:off + k].view_as(self.views[n]))
-        return out
+            moments["linear.weight"] = (self.m_w.view(-1, 1), self.v_w.view(-1, 1))
+        return moments
 
     # --------------------------------------------------------------------- buffers ---
     def _buffers(self, B: int, F: int) -> _Bufs:
@@ -652,16 +481,6 @@ class FusedCTRTrainer:
         with self._scratch.scope():  # this trainer's own scratch (hip_ops.Workspace)
             loss = self._step(x, y, global_batch, next_x, next_y)
             return loss.clone() if return_loss else None
-
-    def reset_loss_sum(self) -> None:
-        """Zero the device loss accumulator (on the current stream, in step order)."""
-        self.loss_sum.zero_()
-
-    def read_loss_sum(self) -> float:
-        """The sum of every step's mean loss since reset_loss_sum(), accumulated on the
-        device in float64 in step order: bitwise the reference's per-step
-        ``total_loss += loss.item()`` (all_main/pretrain_main.py:79). Syncs once."""
-        return float(self.loss_sum.item())
 
     def _step(self, x: torch.Tensor, y: torch.Tensor, global_batch: int | None = None,
               next_x=None, next_y=None) -> torch.Tensor:
@@ -928,37 +747,22 @@ class FusedCTRTrainer:
         self._adam_dense(self.step_count, part="mlp", step_dev=self.step_done)
 
     def _graph_step(self, slot: InputSlot, mean_div: float, have: bool):
-        if self.step_table.capacity < self.step_count + 2:
-            self.step_table.ensure(max(self.step_count + 2, 2 * self.step_table.capacity))
-        if self._graph_tab_version != self.step_table.version:
-            torch.cuda.synchronize(self.device)  # none may still run when destroyed
-            self._graphs.clear()  # they hold the old table's address
-            self._graph_tab_version = self.step_table.version
+        self._sync_step_table()
         mlp = getattr(self.model, "mlp", None)
         drops = tuple(float(mlp[i].p) for i in (2, 5)) if mlp is not None else ()
         pipe = self._pipe_state(slot)
         key = (slot.shape, slot.index, mean_div, self.model.training, drops, have,
                pipe[0], None if pipe[1] is None else (pipe[1][0].B, pipe[1][2]))
         hit = self._graphs.get(key)
-        if hit is None:
-            # the real step (sizes every buffer), then the same launches captured
-            loss = self._launch(slot.ids, slot.y, mean_div, have, plan=slot.plan, pipe=pipe)
-            self._after_step()
-            if len(self._graphs) < self.max_graphs:
-                g = torch.cuda.CUDAGraph()
-                with graph_capture(g, pool=live_pool(self), stream=self._capture_stream):
-                    self._launch(slot.ids, slot.y, mean_div, have, plan=slot.plan, pipe=pipe)
-                self._graphs[key] = (g, self._bufs)
-                self.captures += 1
-            return loss
-        g, self._bufs = hit  # the buffer set the graph was captured with
-        self._bufs.plan = slot.plan
-        if self._bufs.xps is not None:  # the buffer the graph's gather writes
-            self._bufs.xp = self._bufs.xps[pipe[0]]
-            self._bufs.xp_idx = pipe[0]
-        g.replay()
-        self._after_step()
-        return self._bufs.loss
+        if hit is None:  # the launch closure on a miss only: the host paces small batches
+            return self._replay_or_capture(key, lambda: self._launch(
+                slot.ids, slot.y, mean_div, have, plan=slot.plan, pipe=pipe))
+        b = hit[1]  # the buffer set the graph was captured with
+        b.plan = slot.plan
+        if b.xps is not None:  # the buffer the graph's gather writes
+            b.xp = b.xps[pipe[0]]
+            b.xp_idx = pipe[0]
+        return self._replay_or_capture(key, None)
 
     def _launch(self, x: torch.Tensor, y: torch.Tensor, mean_div: float,
                 have_plan: bool = False, plan: hip_ops.SparsePlanBuffers | None = None,
@@ -978,10 +782,7 @@ class FusedCTRTrainer:
             b.xp = self._xp_for(b, pipe[0])
             b.xp_idx = pipe[0]
         b.ev_tail = None
-        y = y.reshape(-1)
-        if y.dtype != torch.float32:
-            y = y.float()
-        y = y.contiguous()
+        y = self._float_labels(y)
         spec = self.spec
         E, bias = self._table().data, self.views.get("bias")
         w = self.model.linear.weight.data if spec.linear else None
@@ -1255,7 +1056,3 @@ class FusedCTRTrainer:
                                  rowmap=None if self.deferred else self.rowmap, out=b.g_rows,
                                  out_lin=b.g_lin)
         return b.g_rows, b.g_lin
-
-    def check_errors(self) -> None:
-        """Raise IndexError if any kernel saw a feature id outside [0, V). Syncs."""
-        hip_ops.check_index_error(self.err)
